@@ -18,7 +18,15 @@ Other configs (--config): C2 (4,096 docs x 10k ops per GPU, weak), C3 (65,536 do
 annotate, forced ties and overlapping removes, per GPU, weak), C5 (1,024 docs x 1M ops, MSN lag <= 64
 so zamboni runs continuously, strided over the ranks, strong).
 
-Prints ONE JSON line (rank 0). Exits non-zero if a document fails or the oracle check disagrees.
+A plain run does only what the headline figure needs: generate the batch on the GPU, warm up, time
+`--steps` replays and print ONE JSON line (rank 0) with the ops/s value and `ms_per_step`. `--full`
+adds everything else the line has carried: the roofline of the pass (algorithmic bytes over the
+HIP-event pass time, which needs the op records on the host), the final summary gather, the oracle
+check of a sample of documents, the CPU baseline and the catch-up probe. `--dump-outputs DIR` writes
+what the last timed step computed (see dump_outputs). The generator is seeded by GEN_SEED and the
+global document ids alone, so the same arguments give the same inputs in every run and build.
+
+Exits non-zero if a document fails or (`--full`) the oracle check disagrees.
 """
 import argparse
 import ctypes
@@ -49,6 +57,7 @@ CONFIGS = {
            "desc": "1M-op docs, C2 mix with MSN lag <= 64 (continuous zamboni)"},
 }
 GEN_SEED = 1000  # one seed for every rank: documents differ by global id only
+DUMP_SEED, DUMP_TEXT_DOCS, DUMP_MAX_BYTES = 20240, 1024, 64 << 20  # --dump-outputs: text sample and size cap
 
 
 def ops_to_messages(ops, pay, lo, hi):
@@ -115,21 +124,63 @@ def catchup_probe(args, n_docs=16, n_ops=20000):
             "other": n_docs - st.count(0) - st.count(1) - st.count(4), "seconds": round(time.time() - t0, 2)}
 
 
+def dump_outputs(path, st, summ, eng):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as .npy files a
+    second build's run with the same arguments can be compared against value for value.
+      stats.npy         float64 [docs, ops, messages, failed_docs] of the last replay()
+      summaries.npy     float64 (n_docs, 8): checksum high 32 bits, checksum low 32 bits, ops, length,
+                        segments, snapshot_bytes, status, doc_id of every document (mte_summaries; the
+                        checksum covers the document's text and its SnapshotV1 bytes; every column is
+                        an integer below 2^32, exact in float64)
+      text_docs.npy     float64 (k, 3): document index, offset and length in text_sample.npy
+      text_sample.npy   float32 UTF-16 code units of the final text of a fixed seeded sample of
+                        documents (the longest one included), concatenated
+    At most DUMP_MAX_BYTES in all: the text sample stops where the budget would be passed."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = len(summ)
+    np.save(os.path.join(path, "stats.npy"),
+            np.array([st["docs"], st["ops"], st["messages"], st["failed_docs"]], dtype=np.float64))
+    cols = [summ["checksum"] >> np.uint64(32), summ["checksum"] & np.uint64(0xFFFFFFFF), summ["ops"], summ["length"],
+            summ["segments"], summ["snapshot_bytes"], summ["status"], summ["doc_id"]]
+    table = np.stack([c.astype(np.float64) for c in cols], axis=1)
+    np.save(os.path.join(path, "summaries.npy"), table)
+    budget = DUMP_MAX_BYTES - table.nbytes - (1 << 20)  # 1 MiB for the headers and the small arrays
+    pick = np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_TEXT_DOCS, n), replace=False)
+    docs = sorted(set(int(d) for d in pick) | ({int(np.argmax(summ["ops"]))} if n else set()))
+    index, parts, off = [], [], 0
+    for d in docs:
+        if int(summ["status"][d]) != 0 or (off + int(summ["length"][d])) * 4 > budget:
+            continue
+        t = np.frombuffer(eng.text(d).encode("utf-16-le", "surrogatepass"), dtype="<u2").astype(np.float32)
+        index.append((d, off, len(t)))
+        parts.append(t)
+        off += len(t)
+    np.save(os.path.join(path, "text_docs.npy"), np.array(index, dtype=np.float64).reshape(-1, 3))
+    np.save(os.path.join(path, "text_sample.npy"), np.concatenate(parts) if parts else np.zeros(0, np.float32))
+    log(f"outputs of the last timed step written to {path}: {n} summary records, text of {len(index)} documents")
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--config", default="C4", choices=sorted(CONFIGS))
     ap.add_argument("--steps", type=int, default=None, help="timed steps (config default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: roofline of the pass, summary gather, oracle check, CPU baseline, catch-up probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (config default)")
     ap.add_argument("--docs", type=int, default=None)
     ap.add_argument("--ops", type=int, default=None)
     ap.add_argument("--clients", type=int, default=8)
-    ap.add_argument("--catchup-probe", type=int, default=1, help="0: skip the catch-up outcome probe")
+    ap.add_argument("--catchup-probe", type=int, default=1, help="(--full) 0: skip the catch-up outcome probe")
     ap.add_argument("--kind", type=int, default=None)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
-    ap.add_argument("--cpu-threads", type=int, default=None, help="default: one per host core available")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--verify-docs", type=int, default=32, help="docs checked against the oracle after timing")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) target CPU-baseline sample duration")
+    ap.add_argument("--cpu-threads", type=int, default=None, help="(--full) default: one per host core available")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--verify-docs", type=int, default=32, help="(--full) docs checked against the oracle after timing")
     ap.add_argument("--opt", action="append", default=[], help="engine option key=value (A/B runs; repeatable)")
     a = ap.parse_args(argv)
     c = CONFIGS[a.config]
@@ -138,6 +189,8 @@ def parse(argv=None):
     a.kind = c["kind"] if a.kind is None else a.kind
     a.steps = c["steps"] if a.steps is None else a.steps
     a.warmup = c["warmup"] if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
 
 
@@ -206,7 +259,6 @@ def launch(args, argv):
 
 
 def run(args):
-    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -217,7 +269,7 @@ def run(args):
         torch.cuda.set_device(local)
         dist.init_process_group("nccl")  # RCCL; carries only barriers, the max-time reduce and the RCCL id
     from fluidframework_amd import mte
-    from fluidframework_amd.shard import gather_summaries_rccl, plan_shard
+    from fluidframework_amd.shard import plan_shard
 
     cfg = CONFIGS[args.config]
     eng = mte.Engine(local)
@@ -231,11 +283,8 @@ def run(args):
                  doc_ids=ids)
     gen_s = time.time() - t0
     log(f"rank {rank}/{world}: generated {n_local} docs ({args.config}, {int(counts.sum())} ops) in {gen_s:.1f} s")
-    batch = eng.export_batch()
-    ops_np = mte.batch_ops(batch)
-    ins = ops_np["type"] == mte.MTE_OP_INSERT
-    payload_chars = int(ops_np["b"][ins].sum())
-    n_ops_rank = int(len(ops_np))
+    # the op records on the host: the roofline's payload bytes, the oracle's and the CPU baseline's input
+    batch = eng.export_batch() if args.full else None
 
     for _ in range(args.warmup):
         w = eng.replay()
@@ -277,10 +326,73 @@ def run(args):
     info = eng.run_info()
     solo = [eng.doc_result(d) for d in range(min(info["solo"], n_local))]
 
+    roofline = cpu = None
+    more = {"gen_s": gen_s}
+    if args.full or (args.dump_outputs and rank == 0):
+        t1 = time.time()
+        summ = eng.summaries()  # this rank's records: checksum of text + SnapshotV1 bytes per document
+        more["summary_s"] = time.time() - t1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st, summ, eng)
+    if args.full:
+        roofline, cpu, full_extra = full_measurements(args, eng, batch, ids, counts, kms, summ, world, rank)
+        more.update(full_extra)
+
+    if rank == 0:
+        line = {
+            "metric": METRIC, "value": value, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": cfg["scaling"],
+            "vs_baseline": None, "dtype": "int32", "data": "synthetic (GPU generator, SURVEY §8d)",
+            "config": {"workload": f"{args.config}: {args.docs} docs"
+                                   + (" per GPU" if cfg["scaling"] == "weak" else " per job")
+                                   + (f" x {args.ops} ops" if args.ops else f", {total_ops} ops")
+                                   + f", {cfg['desc']}, {args.clients} writers",
+                       "config_id": args.config, "docs_per_gpu": n_local, "ops_per_doc": args.ops or "zipf",
+                       "ops_per_step": total_ops, "clients": args.clients, "parallelism": f"doc-sharded x{world}"},
+            "roofline": roofline,  # --full
+            "cpu_baseline": cpu,  # --full
+            "extra": {"ops_per_step_rank0": ops_applied, "longest_doc_ops": int(counts.max()),
+                      "solo_docs": info["solo"], "solo_modes": [r["mode"] for r in solo],
+                      "solo_ms_last_step": info.get("solo_us", 0) / 1000.0,  # critical-path workgroups' pass
+                      "kernel_ms_steps": [round(x, 1) for x in kms],
+                      "solo_ms_steps": [round(x, 1) for x in solo_steps],
+                      # per step: the critical wave's shader cycles (G) and its clock (cycles / 100 MHz
+                      # reference ticks): a slow step with the same cycles ran at a lower clock
+                      "solo_gcycles_steps": [round(c / 1e9, 4) for c, _, _ in solo_clk],
+                      "solo_clock_ghz_steps": [round(c / (r / 100e6) / 1e9, 4) if r else None for c, r, _ in solo_clk],
+                      # the critical wave's start after the bulk kernel's first wave (ms, 100 MHz clock)
+                      "solo_start_delay_ms_steps": [round(dl / 1e5, 3) for _, _, dl in solo_clk],
+                      "lds_ms_last_step": info.get("lds_ms", 0.0), "hbm_ms_last_step": info.get("hbm_ms", 0.0),
+                      "solo_lead_ms": info.get("solo_lead_us", 0) / 1000.0,  # pass start -> solo start
+                      "solo_tail_ms": info.get("solo_tail_us", 0) / 1000.0,  # solo end -> pass end
+                      "us_per_op_critical_path": (info.get("solo_us", 0) / max(int(counts.max()), 1)) if info["solo"] else None,
+                      "docs_rerun_hbm": info["spilled"], "docs_continued_hbm": info["continued"],
+                      "docs_hbm_waves": info["hbm_docs"], "lds_groups": info["lds_groups"],
+                      "hbm_wave_slots": info["hbm_waves"], "rows_waves_per_cu": eng.get_info("rows"),
+                      **more},
+        }
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, eng, batch, ids, counts, kms, summ, world, rank):
+    """--full: what the line carries besides the headline figure. Returns (roofline, cpu_baseline,
+    extra entries). Exits with status 4 if the oracle disagrees with the GPU's summaries."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from fluidframework_amd import mte
+    from fluidframework_amd.shard import gather_summaries_rccl
+
+    n_local = len(ids)
+    ops_np = mte.batch_ops(batch)
+    ins = ops_np["type"] == mte.MTE_OP_INSERT
+    payload_chars = int(ops_np["b"][ins].sum())
+    n_ops_rank = int(len(ops_np))
+
     # final summary gather (RCCL all-gather of 32-B records), outside the timed region
-    t1 = time.time()
-    summ = eng.summaries()  # this rank's records: checksum of text + SnapshotV1 bytes per document
-    snap_host_s = time.time() - t1
     gathered = len(gather_summaries_rccl(eng)) if world > 1 else len(summ)
     snap_bytes = int(summ["snapshot_bytes"].sum())
 
@@ -347,48 +459,13 @@ def run(args):
 
     probe = catchup_probe(args) if rank == 0 and args.catchup_probe else None
 
-    if rank == 0:
-        line = {
-            "metric": METRIC, "value": value, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": cfg["scaling"],
-            "vs_baseline": None, "dtype": "int32", "data": "synthetic (GPU generator, SURVEY §8d)",
-            "config": {"workload": f"{args.config}: {args.docs} docs"
-                                   + (" per GPU" if cfg["scaling"] == "weak" else " per job")
-                                   + (f" x {args.ops} ops" if args.ops else f", {total_ops} ops")
-                                   + f", {cfg['desc']}, {args.clients} writers",
-                       "config_id": args.config, "docs_per_gpu": n_local, "ops_per_doc": args.ops or "zipf",
-                       "ops_per_step": total_ops, "clients": args.clients, "parallelism": f"doc-sharded x{world}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "measured_peak_gbs": HBM_MEASURED_GBS,
-                         "kernel": "replay pass: mte::k_solo + mte::k_rows (the bulk; k_lds / k_hbmq for batches the rows cannot take) + mte::k_rows_cont (concurrent streams) + SnapshotV1 emission (mte::k_emit_count/k_emit_write, overlapped with k_solo)",
-                         "kernel_ms": kernel_ms, "alg_bytes_per_launch": alg_bytes},
-            "cpu_baseline": cpu,
-            "extra": {"ops_per_step_rank0": ops_applied, "longest_doc_ops": int(counts.max()),
-                      "solo_docs": info["solo"], "solo_modes": [r["mode"] for r in solo],
-                      "solo_ms_last_step": info.get("solo_us", 0) / 1000.0,  # critical-path workgroups' pass
-                      "kernel_ms_steps": [round(x, 1) for x in kms],
-                      "solo_ms_steps": [round(x, 1) for x in solo_steps],
-                      # per step: the critical wave's shader cycles (G) and its clock (cycles / 100 MHz
-                      # reference ticks): a slow step with the same cycles ran at a lower clock
-                      "solo_gcycles_steps": [round(c / 1e9, 4) for c, _, _ in solo_clk],
-                      "solo_clock_ghz_steps": [round(c / (r / 100e6) / 1e9, 4) if r else None for c, r, _ in solo_clk],
-                      # the critical wave's start after the bulk kernel's first wave (ms, 100 MHz clock)
-                      "solo_start_delay_ms_steps": [round(dl / 1e5, 3) for _, _, dl in solo_clk],
-                      "lds_ms_last_step": info.get("lds_ms", 0.0), "hbm_ms_last_step": info.get("hbm_ms", 0.0),
-                      "solo_lead_ms": info.get("solo_lead_us", 0) / 1000.0,  # pass start -> solo start
-                      "solo_tail_ms": info.get("solo_tail_us", 0) / 1000.0,  # solo end -> pass end
-                      "us_per_op_critical_path": (info.get("solo_us", 0) / max(int(counts.max()), 1)) if info["solo"] else None,
-                      "docs_rerun_hbm": info["spilled"], "docs_continued_hbm": info["continued"],
-                      "docs_hbm_waves": info["hbm_docs"], "lds_groups": info["lds_groups"],
-                      "hbm_wave_slots": info["hbm_waves"], "rows_waves_per_cu": eng.get_info("rows"),
-                      "gen_s": gen_s, "summary_s": snap_host_s,
-                      "snapshot_bytes": snap_bytes, "summaries_gathered": gathered, "oracle_verified_docs": nv,
-                      "catchup_probe": probe},
-        }
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "measured_peak_gbs": HBM_MEASURED_GBS,
+                "kernel": "replay pass: mte::k_solo + mte::k_rows (the bulk; k_lds / k_hbmq for batches the rows cannot take) + mte::k_rows_cont (concurrent streams) + SnapshotV1 emission (mte::k_emit_count/k_emit_write, overlapped with k_solo)",
+                "kernel_ms": kernel_ms, "alg_bytes_per_launch": alg_bytes}
+    return roofline, cpu, {"snapshot_bytes": snap_bytes, "summaries_gathered": gathered,
+                           "oracle_verified_docs": nv, "catchup_probe": probe}
 
 
 def main():

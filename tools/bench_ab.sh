@@ -4,6 +4,7 @@
 #   (config:opt[,opt...]; an empty opt list = the default engine options)
 set -o pipefail
 T=${T:-bab}
+EXTRA="--full ${EXTRA:-}"  # the line's cpu_baseline (printed below) and oracle check
 mkdir -p gpurun_out/$T
 for spec in "$@"; do
   cfg=${spec%%:*}; opts=${spec#*:}

@@ -5,7 +5,7 @@
 # Usage: tools/profile.sh <tag> [bench args...]
 set -euo pipefail
 TAG=${1:-r01}; shift || true
-ARGS=${@:---steps 2 --warmup 0 --no-cpu-baseline --verify-docs 2}
+ARGS=${@:---full --steps 2 --warmup 0 --no-cpu-baseline --verify-docs 2}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
