@@ -1,6 +1,6 @@
 """Unbounded client ids (client.ts:644-668 getOrAddShortClientId never forgets a client; a container
 log gets a new clientId on every reconnect): the builder maps clients to the engine's 128 slots and
-reuses a slot once minSeq has passed every op of its client (mte_host.cpp DocBuild::short_id); a
+reuses a slot once minSeq has passed every op of its client (builder.cpp DocBuild::short_id); a
 window of more than 64 clients keeps removedClientOverlap of clients 64..127 in a second per-segment
 mask (engine.hpp ovl2). CPU:
 the oracle's record path (slot ids) against its JSON path (real ids, no cap); GPU: the engine against

@@ -8,11 +8,10 @@ B=../_build
 declare -A S=([apply]=2 [resolve]=3 [insert_slot]=4 [split]=5 [range]=6 [zamboni]=7 [scour]=8 [heap]=9 \
               [find_seg]=10 [pack]=11 [lru]=12 [split_at]=21 [op_ins]=22 [op_rem]=23 [zam_msn]=24 [zam_edit]=25)
 build() {
-  mkdir -p $B/rp_$1
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable \
-    -mllvm -amdgpu-sched-strategy=iterative-ilp -DMTE_PROFILE -DRG_PROF_ONLY=$2 -c mte_solo.hip -o $B/rp_$1/mte_solo.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/rp_$1/libmte.so $B/prof/mte_kernels.o $B/rp_$1/mte_solo.o $B/emit.o \
-    $B/prof/mte_host.o -lpthread
+  # mte_solo.o alone into rp_<name>, the prof build's other objects, the Makefile's link rule
+  rm -f $B/rp_$1/mte_solo.o
+  make -s B=$B/prof SOLO=$B/rp_$1 \
+    CXXFLAGS="-O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable -DMTE_PROFILE -DRG_PROF_ONLY=$2"
 }
 n=0
 for k in "${!S[@]}"; do

@@ -7,9 +7,8 @@ cd "$(dirname "$0")/../fluidframework_amd/csrc"
 B=../_build
 V=$1; shift
 make -s -C . >/dev/null
-mkdir -p $B/$V
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable ${SOLOFLAGS--mllvm -amdgpu-sched-strategy=iterative-ilp} "$@" \
-  -c mte_solo.hip -o $B/$V/mte_solo.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/$V/libmte.so $B/mte_kernels.o $B/$V/mte_solo.o $B/emit.o \
-  $B/mte_host.o -lpthread
+# mte_solo.o alone into $B/$V (always recompiled: the flags differ from run to run), the default
+# build's other objects, the Makefile's link rule; each extra flag stays one word
+rm -f $B/$V/mte_solo.o
+make -s SOLO=$B/$V SOLOFLAGS="${SOLOFLAGS--mllvm -amdgpu-sched-strategy=iterative-ilp} ${*@Q}"
 echo "$B/$V/libmte.so"
