@@ -157,7 +157,7 @@ struct St {
 };
 
 // FULL = false: the instantiation for batches that use no property sets, no client id above 31 and no
-// '\n' in any payload (the host checks, mte_host.cpp batch_is_lean): property maps, the HBM half of
+// '\n' in any payload (the host checks, engine_load.cpp mte_load's scan): property maps, the HBM half of
 // the overlap masks and TextSegment.canAppend's newline test compile out, which leaves the replay
 // loop fewer live registers. Same results on such batches (tests/test_gpu_c4.py).
 // LVL 0: the lean instantiation (FULL = false); 1: FULL; 2: FULL + EXT, the extensions few batches use

@@ -1,4 +1,4 @@
-// gather_plan.hpp — the host-side arithmetic of mte_gather_summaries (mte_host.cpp): RCCL's
+// gather_plan.hpp — the host-side arithmetic of mte_gather_summaries (gather.cpp): RCCL's
 // all-gather moves equal-sized blocks, so every rank sends its summary records padded to the largest
 // rank's count, and the gathered blocks are concatenated back in rank order without the padding.
 // Header-only and free of HIP/RCCL types, so the CPU suite checks it with a fake all-gather

@@ -1,4 +1,4 @@
-// Kernel launchers (mte_kernels.hip) used by the host side (mte_host.cpp). full: the engine level
+// Kernel launchers (mte_kernels.hip) used by the host side (engine_run.cpp). full: the engine level
 // (0 lean, 1 FULL, 2 FULL + EXT; engine.hpp).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2291,7 +2291,7 @@ struct RegEngine {
     // Client.applyMsg is incremental (client.ts:805-836): a reader interleaves getText with messages.
     // With Params::ck_out set, a document this engine finishes also leaves its whole replay state in
     // its checkpoint region (DocCfg::ck_out_off, ck_cap words); a later pass over a log that extends
-    // this one (the host checks the prefix, mte_host.cpp ck_match) starts from that state at op
+    // this one (the host checks the prefix, engine_run.cpp ck_match) starts from that state at op
     // ck_at instead of op 0. The state is the engine's own: rows, interior levels, heap, scalars, the
     // live merge-arena semispace and the property maps -- nothing the replay does depends on where it
     // started, so the continued replay is the full one, op for op.

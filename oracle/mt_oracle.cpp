@@ -1669,7 +1669,7 @@ class Doc {
         }
         uint32_t below(uint32_t n) { return (uint32_t)(((next() >> 32) * (uint64_t)n) >> 32); }
     };
-    // The generator's property sets in the host's interning order (mte_host.cpp
+    // The generator's property sets in the host's interning order (engine_load.cpp
     // build_generator_props): ids 1..28 one key, then every two-key set.
     static constexpr uint32_t kGenPropsets = 28 + 6 * 49;
     static JObj genPropset(uint32_t id) {

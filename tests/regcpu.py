@@ -79,7 +79,7 @@ def replay(ops, pay, arena_cap=None, pool_rows=None):
 
 
 class GenProps:
-    """The generator's property sets (mte_host.cpp build_generator_props, the oracle's genPropset):
+    """The generator's property sets (engine_load.cpp build_generator_props, the oracle's genPropset):
     ids 1..28 one key, then 294 two-key sets; value id 0 = null. Interned tables for the engine and
     the oracle's batch."""
     KEYS = ["bold", "italic", "color", "size"]
@@ -176,7 +176,7 @@ def replay_split(ops, pay, cut, kind=0, pool_rows=16, gp=None, map_words=16, are
 
 
 def rows_json(rows, text, names, props=None):
-    """The engine's rows as mte_segments_json renders them (host DocView, mte_host.cpp)."""
+    """The engine's rows as mte_segments_json renders them (host DocView, readback.cpp)."""
     vis, aux, ovl = rows
     out = []
     for i in range(len(vis)):
