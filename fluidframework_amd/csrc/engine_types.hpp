@@ -271,10 +271,14 @@ struct Params {
 constexpr u32 ROWS_CONT_WORDS = 32;
 
 // A checkpoint region (option retain, reg_engine.hpp ckpt_save): header, up to CK_MAX_ROWS rows of up
-// to 10 fields, 24 registers, the arena semispace (u16 units) and the map records, in words.
+// to ROW_FIELDS_MAX fields, RG_STATE_REGS registers, the arena semispace (u16 units) and the map
+// records, in words. (The row engine's stored state, reg_engine.hpp: a field or register is 64 words.)
 constexpr u32 CK_MAX_ROWS = 32, CK_HDR_WORDS = 64;
+constexpr u32 ROW_FIELDS_MAX = 10;  // fields of a slot row: 8, + the property map id, + removers 32..63
+constexpr u32 RG_STATE_REGS = 24;   // interior levels, heap keys, heap segment ids: 8 registers each
 MTE_HOSTDEV_ u64 ck_region_words(u32 arena_cap, u32 map_cap, u32 map_words) {
-    return CK_HDR_WORDS + (u64)CK_MAX_ROWS * 10 * 64 + 24 * 64 + ((u64)arena_cap + 1) / 2 + (u64)map_cap * map_words;
+    return CK_HDR_WORDS + (u64)CK_MAX_ROWS * ROW_FIELDS_MAX * 64 + RG_STATE_REGS * 64 + ((u64)arena_cap + 1) / 2 +
+           (u64)map_cap * map_words;
 }
 
 constexpr u32 SOLO_CLK_SLOTS = 64;  // solo workgroups with clock stamps (Params::solo_clk)

@@ -6,6 +6,14 @@
 #include "engine_types.hpp"
 
 namespace mte {
+// Kernel instantiations: the generator always runs the FULL engine (its C3 kind uses properties);
+// a replay runs the lean one (level 0) when the host found the batch free of the optional features,
+// the EXT one (level 2) when it carries catch-up records or permutation runs, else FULL (level 1)
+// (engine_load.cpp mte_load).
+#define MTE_PICK(K, gen, lvl)                                                                           \
+    ((gen) ? (const void*)K<true, 1> : (lvl) >= 2 ? (const void*)K<false, 2> : (lvl) == 1 ? (const void*)K<false, 1> \
+                                                                               : (const void*)K<false, 0>)
+
 hipError_t launch_lds(const Params& p, bool gen, int full, u32 n_groups, hipStream_t s);
 hipError_t launch_solo(const Params& p, bool gen, int full, u32 n_solo, bool ck, hipStream_t s);
 // wait (one wave, <= 20 ms) until `n_solo` solo workgroups have started: issued on the bulk's stream
@@ -14,7 +22,7 @@ hipError_t launch_solo_gate(const u32* started, u32 n_solo, hipStream_t s);
 hipError_t launch_rows(const Params& p, u32 waves_per_cu, u32 n_groups, bool props, bool wide, bool ck, hipStream_t s);
 hipError_t launch_hbmq(const Params& p, bool gen, int full, u32 n_waves, hipStream_t s);
 hipError_t launch_rows_cont(const Params& p, bool props, bool wide, u32 n_slots, hipStream_t s);
-extern const u64 ROWS_DUMP_BYTES;  // a slot must hold k_rows' state dump (mte_solo.hip RowsDump)
+extern const u64 ROWS_DUMP_BYTES;  // a slot must hold k_rows' state dump (reg_engine.hpp DUMP_BYTES)
 hipError_t launch_hbm(const Params& p, bool gen, int full, u32 n_docs, hipStream_t s);
 hipError_t launch_wave_selftest(const u32* in, u32* out, u32 n_waves, hipStream_t s);
 }  // namespace mte

@@ -205,14 +205,6 @@ __global__ __launch_bounds__(64) void k_wave_selftest(const u32* in, u32* out) {
     o[256 + L] = (u32)group8_max((i32)v);
 }
 
-// Kernel instantiations: the generator always runs the FULL engine (its C3 kind uses properties);
-// a replay runs the lean one (level 0) when the host found the batch free of the optional features,
-// the EXT one (level 2) when it carries catch-up records or permutation runs, else FULL (level 1)
-// (engine_load.cpp mte_load).
-#define MTE_PICK(K, gen, lvl)                                                                           \
-    ((gen) ? (const void*)K<true, 1> : (lvl) >= 2 ? (const void*)K<false, 2> : (lvl) == 1 ? (const void*)K<false, 1> \
-                                                                               : (const void*)K<false, 0>)
-
 template <class Plan>
 static hipError_t lds_attr(const void* k) {
     return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Plan));

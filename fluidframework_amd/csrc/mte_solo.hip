@@ -57,7 +57,7 @@ MTE_DEV void solo_doc(const Params& p) {
         // lean replay: the whole document state in this wave's registers (reg_engine.hpp); it moves
         // to the LDS plan below only if it outgrows the registers or reaches an op they do not cover
         if (p.reg_solo) {
-            RegEngine<> r(p, d);
+            RegEngine<> r(p, d, RowsLds::solo_lean());
             if constexpr (CK) at = r.ckpt_resume(at);  // the previous pass's state, if this log extends it
             at = r.replay(at, p.docs[d].op_end);
             if (r.status != REG_HANDOFF) {
@@ -74,15 +74,10 @@ MTE_DEV void solo_doc(const Params& p) {
             handed = true;
         }
     } else if constexpr (!GEN && LVL == 1) {
-        // FULL replay (properties, clients up to 63): the PROPS + WIDE row engine, its map ids and
-        // high removers in arrays past the rows' slots in the SoloPlan's aux array (blocks
-        // RG_BLOCKS.., unused until a handoff has read them)
+        // FULL replay (properties, clients up to 63): the PROPS + WIDE row engine (WIDE: clients
+        // 32..63 too, a second removers word per slot)
         if (p.reg_solo) {
-            constexpr u32 vb = (u32)offsetof(SoloPlan, vis), ab = (u32)offsetof(SoloPlan, aux);
-            static_assert(RG_BLOCKS * 8 * 16 + 2 * RG_BLOCKS * 8 * 4 <= SOLO_POOL * 8 * 16, "props / rm2 arrays in the aux pool");
-            // WIDE: clients 32..63 too (a second removers array after the map ids)
-            RegEngine<(int)RG_ROWS, false, true, true> r(p, d, vb, ab, 4, 0, ab + RG_BLOCKS * 8 * 16,
-                                                         ab + RG_BLOCKS * 8 * 16 + RG_BLOCKS * 8 * 4);
+            RegEngine<(int)RG_ROWS, false, true, true> r(p, d, RowsLds::solo_full());
             if constexpr (CK) at = r.ckpt_resume(at);
             if (!r.status) at = r.replay(at, p.docs[d].op_end);
             if (r.status != REG_HANDOFF) {
@@ -162,22 +157,7 @@ __global__ __launch_bounds__(64 * SOLO_WAVES) __attribute__((amdgpu_waves_per_eu
 // HBM-resident in the pass (rows_continue); one the pool cannot grow in the middle of an op restarts
 // from its first op (the restart queue) or is re-run by the host (DOC_SPILL). WIDE: batches with writers 32..63 (a second removers
 // word per slot, as k_solo's FULL row engine).
-// LDS geometry of k_rows: 32 B per slot (vis + aux), +4 with the property map ids (PROPS), +4 with
-// the removers 32..63 (WIDE). The pool (8 / 12 waves): vis array, aux array, [props array], [rm2
-// array], row mask. Fixed quarters (4 waves): per wave its rows' vis, aux, [props] and [rm2] arrays.
-template <bool PROPS, bool WIDE>
-struct RowsGeom {
-    static constexpr u32 SLOT = 32 + (PROPS ? 4 : 0) + (WIDE ? 4 : 0);  // LDS bytes per slot
-    static constexpr u32 POOL = (LDS_BYTES - ROWS_POOL_WORDS * 4) / (64 * SLOT);  // 79, 71 or 63 rows
-    static constexpr u32 VIS = 0, AUX = POOL * 64 * 16, PRP = 2 * POOL * 64 * 16;
-    static constexpr u32 RM2 = PRP + (PROPS ? POOL * 64 * 4 : 0);
-    static constexpr u32 MASK = RM2 + (WIDE ? POOL * 64 * 4 : 0);
-    static constexpr u32 LDS = MASK + ROWS_POOL_WORDS * 4;
-    static constexpr u32 FIXED_NR = LDS_BYTES / 4 / (64 * SLOT);  // 20, 17 or 16 rows per wave
-    static constexpr u32 FIXED_WAVE = FIXED_NR * 64 * SLOT;
-    static constexpr u32 FIXED_LDS = 4 * FIXED_WAVE;
-    static_assert(LDS <= LDS_BYTES && FIXED_LDS <= LDS_BYTES && POOL <= 32 * ROWS_POOL_WORDS, "k_rows LDS plan");
-};
+// (LDS geometry: reg_rows.hpp RowsGeom.)
 // A k_rows document that outgrows the row plan (or reaches an op the row engine does not implement)
 // between two ops continues in the same pass, HBM-resident: the wave claims a free HBM slot
 // (Params::spill, the bitmap slot_bits over n_hslots slots; k_lds / k_hbmq do not run beside k_rows),
@@ -224,65 +204,23 @@ MTE_DEV u32 try_hslot(const Params& p) {
     }
     return NONE;
 }
-// The dump in a slot: logical row rr's field f (len, seq, rseq, meta, cap, toff, rm, sid, [props],
-// [rm2]) at words ((rr * NF + f) * 64 + lane), then LV, HK and HS (8 registers each) from word
-// RG_ROWS * NF * 64; the record: doc, slot, op index (lo, hi), then the scalars below.
-template <bool PROPS, bool WIDE>
-struct RowsDump {
-    static constexpr u32 NF = 8 + (PROPS ? 1u : 0u) + (WIDE ? 1u : 0u);
-    static constexpr u32 REGS = (u32)RG_ROWS * NF * 64;
-    static constexpr u64 BYTES = (u64)(REGS + 24 * 64) * 4;
-};
-const u64 ROWS_DUMP_BYTES = RowsDump<true, true>::BYTES;  // (mte_kernels.h: the host checks slots against it)
-enum : u32 { RD_NLB = 4, RD_HEIGHT, RD_HEAPSIZE, RD_HEAPTOP, RD_MINSEQ, RD_CURSEQ, RD_SEGNEXT, RD_ARENATOP,
-             RD_ARENASEL, RD_MAPNEXT, RD_NOPS, RD_NMSGS, RD_NGC, RD_MAXLB, RD_END };
-static_assert(RD_END <= ROWS_CONT_WORDS, "rows_cont record");
+// The dump in a slot and its queue record: reg_engine.hpp state_dump / state_restore.
+const u64 ROWS_DUMP_BYTES = RegEngine<(int)RG_ROWS, false, true, true>::DUMP_BYTES;  // (mte_kernels.h: the host checks slots against it)
 
 // Returns 0 when the document was queued for k_rows_cont, else why not (DocRes::spill_why's low byte
 // after the caller's mark): 1 no free slot or queue, 3 the rows do not hold the whole state (a PAGED
 // engine that never got its first row)
 template <class R>
 MTE_DEV u32 rows_dump(const Params& p, R& r, u32 d, u64 at) {
-    typedef RowsDump<R::kProps, R::kWide> D;
-    if (!r.rows_whole()) return 3;
+    if (!r.rows.rows_whole(r.n_lb)) return 3;
     if (!p.slot_bits || !p.n_hslots || !p.rows_cont) return 1;
     const u32 slot = try_hslot(p);
     if (slot == NONE) return 1;
-    const u32 L = lane_id();
-    u32* base = reinterpret_cast<u32*>(p.spill + (u64)(p.slot_hbm0 + slot) * p.slot_bytes);
-    const u32 nrows = (r.n_lb + 7) >> 3;
-    for (u32 rr = 0; rr < nrows; rr++) {
-        const auto w = r.ldrow(rr);
-        u32* o = base + (u64)rr * D::NF * 64 + L;
-        o[0] = w.len.x;
-        o[64] = w.seq.x;
-        o[128] = w.rseq.x;
-        o[192] = w.meta.x;
-        o[256] = w.cap.x;
-        o[320] = w.toff.x;
-        o[384] = w.rm.x;
-        o[448] = w.sid.x;
-        if constexpr (R::kProps) o[512] = w.props.x;
-        if constexpr (R::kWide) o[64 * (D::NF - 1)] = w.rm2.x;
-    }
-    u32* g = base + D::REGS + L;
-#pragma unroll
-    for (u32 i = 0; i < 8; i++) {
-        g[64 * i] = r.LV.get(i).x;
-        g[64 * (8 + i)] = r.HK.get(i).x;
-        g[64 * (16 + i)] = r.HS.get(i).x;
-    }
     u32 k = 0;
-    if (L == 0) k = atomicAdd(&p.counters[10], 1u);
+    if (lane_id() == 0) k = atomicAdd(&p.counters[10], 1u);
     k = wave_read(k, 0);
-    u32* rec = p.rows_cont + (u64)k * ROWS_CONT_WORDS;
-    const u32 v = L == 0 ? d : L == 1 ? slot : L == 2 ? (u32)at : L == 3 ? (u32)(at >> 32)
-                : L == RD_NLB ? r.n_lb : L == RD_HEIGHT ? r.height : L == RD_HEAPSIZE ? r.heapSize
-                : L == RD_HEAPTOP ? (u32)r.heapTop : L == RD_MINSEQ ? (u32)r.minSeq : L == RD_CURSEQ ? (u32)r.curSeq
-                : L == RD_SEGNEXT ? r.segNext : L == RD_ARENATOP ? r.arenaTop : L == RD_ARENASEL ? r.arenaSel
-                : L == RD_MAPNEXT ? r.mapNext : L == RD_NOPS ? r.ops_n() : L == RD_NMSGS ? r.msgs_n()
-                : L == RD_NGC ? r.n_gc : r.max_lb;
-    if (L < RD_END) rec[L] = v;
+    r.state_dump(reinterpret_cast<u32*>(p.spill + (u64)(p.slot_hbm0 + slot) * p.slot_bytes),
+                 p.rows_cont + (u64)k * ROWS_CONT_WORDS, d, slot, at);
     // release: the dump and the record before k_rows_cont (another XCD's L2) reads them
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -295,7 +233,6 @@ MTE_DEV u32 rows_dump(const Params& p, R& r, u32 d, u64 at) {
 // (every record holds one); those past the queue exit at once.
 template <bool PROPS, bool WIDE>
 __global__ __launch_bounds__(64) void k_rows_cont(Params p) {
-    typedef RowsDump<PROPS, WIDE> D;
     typedef RegEngine<(int)RG_ROWS, false, PROPS, WIDE> R;
     constexpr int LVL = PROPS ? 1 : 0;
     const u32 L = lane_id();
@@ -305,46 +242,8 @@ __global__ __launch_bounds__(64) void k_rows_cont(Params p) {
     const u32 w = p.rows_cont[(u64)i * ROWS_CONT_WORDS + (L < ROWS_CONT_WORDS ? L : 0u)];
     const u32 d = wave_read(w, 0), slot = wave_read(w, 1);
     const u64 at = (u64)wave_read(w, 2) | ((u64)wave_read(w, 3) << 32);
-    constexpr u32 VB = 0, AB = RG_ROWS * 64 * 16, PB = 2 * RG_ROWS * 64 * 16, R2B = PB + (PROPS ? RG_ROWS * 64 * 4 : 0);
-    R r(p, d, VB, AB, 5, 0, PB, R2B);  // (init: every row zero)
-    r.n_lb = wave_read(w, RD_NLB);
-    r.height = wave_read(w, RD_HEIGHT);
-    r.heapSize = wave_read(w, RD_HEAPSIZE);
-    r.heapTop = (i32)wave_read(w, RD_HEAPTOP);
-    r.minSeq = (i32)wave_read(w, RD_MINSEQ);
-    r.curSeq = (i32)wave_read(w, RD_CURSEQ);
-    r.segNext = wave_read(w, RD_SEGNEXT);
-    r.arenaTop = wave_read(w, RD_ARENATOP);
-    r.arenaSel = wave_read(w, RD_ARENASEL);
-    r.mapNext = wave_read(w, RD_MAPNEXT);
-    r.set_counts(wave_read(w, RD_NOPS), wave_read(w, RD_NMSGS));
-    r.n_gc = wave_read(w, RD_NGC);
-    r.max_lb = wave_read(w, RD_MAXLB);
-    r.status = 0;
-    const u32* base = reinterpret_cast<const u32*>(p.spill + (u64)(p.slot_hbm0 + slot) * p.slot_bytes);
-    const u32 nrows = (r.n_lb + 7) >> 3;
-    for (u32 rr = 0; rr < nrows && rr < RG_ROWS; rr++) {
-        const u32* o = base + (u64)rr * D::NF * 64 + L;
-        typename R::Row x;
-        x.len = simd::V{o[0]};
-        x.seq = simd::V{o[64]};
-        x.rseq = simd::V{o[128]};
-        x.meta = simd::V{o[192]};
-        x.cap = simd::V{o[256]};
-        x.toff = simd::V{o[320]};
-        x.rm = simd::V{o[384]};
-        x.sid = simd::V{o[448]};
-        if constexpr (PROPS) x.props = simd::V{o[512]};
-        if constexpr (WIDE) x.rm2 = simd::V{o[64 * (D::NF - 1)]};
-        r.strow(rr, x);
-    }
-    const u32* g = base + D::REGS + L;
-#pragma unroll
-    for (u32 q = 0; q < 8; q++) {
-        r.LV.set(q, simd::V{g[64 * q]});
-        r.HK.set(q, simd::V{g[64 * (8 + q)]});
-        r.HS.set(q, simd::V{g[64 * (16 + q)]});
-    }
+    R r(p, d, RowsLds::rows_cont<PROPS, WIDE>());  // (init: every row zero)
+    r.state_restore(reinterpret_cast<const u32*>(p.spill + (u64)(p.slot_hbm0 + slot) * p.slot_bytes), simd::V{w});
     // every read of the dump done before the handoff writes the HBM engine's arrays over it
     __builtin_amdgcn_s_waitcnt(0);
     wave_sync();
@@ -369,7 +268,7 @@ __global__ __launch_bounds__(64) void k_rows_cont(Params p) {
 template <bool PROPS, bool WIDE>
 static hipError_t launch_rows_cont_t(const Params& p, u32 n_slots, hipStream_t s) {
     const void* k = (const void*)k_rows_cont<PROPS, WIDE>;
-    constexpr u32 LDS = RG_ROWS * 64 * (32 + (PROPS ? 4 : 0) + (WIDE ? 4 : 0));
+    constexpr u32 LDS = RowsGeom<PROPS, WIDE>::CONT_LDS;
     static const hipError_t attr = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     if (attr != hipSuccess) return attr;
     void* args[] = {(void*)&p};
@@ -398,10 +297,7 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(RW / 4,
                                                            : ~((1u << (np - threadIdx.x * 32)) - 1u);
         __syncthreads();
     }
-    const u32 vb = PAGED ? G::VIS : w * G::FIXED_WAVE;
-    const u32 ab = PAGED ? G::AUX : vb + G::FIXED_NR * 64u * 16u;
-    const u32 pb = PAGED ? G::PRP : vb + G::FIXED_NR * 64u * 32u;
-    const u32 r2b = PAGED ? G::RM2 : pb + (PROPS ? G::FIXED_NR * 64u * 4u : 0u);
+    const RowsLds lds = PAGED ? RowsLds::rows_pool<PROPS, WIDE>() : RowsLds::rows_fixed<PROPS, WIDE>(w);
     if (blockIdx.x == 0 && threadIdx.x == 0 && p.solo_clk) p.solo_clk[4 * SOLO_CLK_SLOTS] = __builtin_amdgcn_s_memrealtime();
     for (;;) {
         // a document another wave gave back when the pool was full restarts first (once; a second
@@ -443,11 +339,11 @@ __global__ __launch_bounds__(64 * RW) __attribute__((amdgpu_waves_per_eu(RW / 4,
             }
             d = p.doc_list[i];
         }
-        RegEngine<PAGED ? (int)RG_ROWS : (int)G::FIXED_NR, PAGED, PROPS, WIDE> r(p, d, vb, ab, 5, G::MASK, pb, r2b);
+        RegEngine<PAGED ? (int)RG_ROWS : (int)G::FIXED_NR, PAGED, PROPS, WIDE> r(p, d, lds);
         u64 at = p.docs[d].op_begin;
         if constexpr (CK) at = r.ckpt_resume(at);
         if (!r.status) at = r.replay(at, p.docs[d].op_end);
-        if (r.status == REG_HANDOFF && PAGED && p.rows_retry && r.pool_full && !again) {
+        if (r.status == REG_HANDOFF && PAGED && p.rows_retry && r.rows.pool_full && !again) {
             // marked for the host's re-run first (so a document no wave restarts is still replayed),
             // then queued to restart from its first op; a restart that finishes overwrites the mark
             r.mark_spilled();
@@ -502,10 +398,6 @@ hipError_t launch_rows(const Params& p, u32 waves_per_cu, u32 n_groups, bool pro
     if (wide) return props ? launch_rows_t<true, true>(p, rw, n_groups, ck, s) : hipErrorInvalidValue;
     return props ? launch_rows_t<true, false>(p, rw, n_groups, ck, s) : launch_rows_t<false, false>(p, rw, n_groups, ck, s);
 }
-
-#define MTE_PICK(K, gen, lvl)                                                                           \
-    ((gen) ? (const void*)K<true, 1> : (lvl) >= 2 ? (const void*)K<false, 2> : (lvl) == 1 ? (const void*)K<false, 1> \
-                                                                               : (const void*)K<false, 0>)
 
 hipError_t launch_solo(const Params& p, bool gen, int full, u32 n_solo, bool ck, hipStream_t s) {
     static const hipError_t attr = [] {

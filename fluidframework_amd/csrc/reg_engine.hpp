@@ -7,7 +7,9 @@
 //     A row is 64 slots = 64 lanes, held in LDS exactly where the LDS engine's SoloPlan keeps slots
 //     (vis = len, seq, removedSeq, meta; aux = -, text offset, text capacity / overlap mask,
 //     segment id): one ds_read_b128 per lane fetches a whole row's visibility fields. An empty slot
-//     has len 0 (segments are never empty), so a block's child count is a popcount of one ballot;
+//     has len 0 (segments are never empty), so a block's child count is a popcount of one ballot.
+//     The rows themselves -- storage, page table, pool, the one-row register cache -- are
+//     reg_rows.hpp's RowStore, which this engine holds as `rows`;
 //   * position resolution (insertingWalk + nodeLength, mergeTree.ts:2345-2474,1659-1699): per row
 //     ONE predicate evaluation for 64 slots and ONE DPP prefix scan; the first block whose
 //     cumulative end reaches pos wins (blocks win ties, :2274-2276), then the slot inside it
@@ -26,30 +28,29 @@
 // A document whose state outgrows this plan, or that reaches an op this engine does not implement
 // (annotate, summary load records, relative positions, legacy catch-up, permutation runs), hands its
 // state to the LDS engine between two ops (reg_handoff.hpp) and continues there.
-// The same source also builds for the CPU (wave_simd.hpp MTE_CPU): the CPU suite checks it against
-// the oracle (tests/test_reg_engine_cpu.py); the product runs the device build only.
+// The same source also builds for the CPU: everything that differs there is behind wave_simd.hpp and
+// reg_rows.hpp (MTE_CPU; in this file it only switches the profile and statistics blocks off or on,
+// and gives the CPU pool's size the name the CPU harness has always set, RegEngine::pool_rows).
+// The CPU suite checks it against the oracle (tests/test_reg_engine_cpu.py); the product runs the
+// device build only.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "engine_types.hpp"
+#include "reg_rows.hpp"
 #include "wave_simd.hpp"
 
 namespace mte {
 
-constexpr u32 RG_ROWS = 32;               // slot rows
-constexpr u32 RG_BLOCKS = RG_ROWS * 8;    // leaf blocks
 constexpr u32 RG_LEVELS = 8;              // interior levels (height <= RG_LEVELS + 1)
 constexpr u32 RG_HEAP = 511;              // LRU heap positions 1..511
 constexpr u32 RSEQ_LIVE = 0x7FFFFFFFu;    // removedSeq of a live segment (never <= a refSeq)
 constexpr u32 RCL_LIVE = 0xFFu;           // removedClient byte of a live segment (never a client)
 constexpr i32 REG_HANDOFF = 101;          // internal: continue in the LDS engine from the current op
-constexpr u32 ROWS_POOL_WORDS = 3;         // k_rows' pool row mask (mte_solo.hip RowsGeom): <= 96 rows
-constexpr u32 ROWS_WAIT_TRIES = 20000;     // a wave finding the pool full retries this often (s_sleep 8)
 // needsScour (mergeTree.ts:63) in meta bits 24..25 of every slot lane of a block
 constexpr u32 NS_SHIFT = 24, NS_MASK = 3u << NS_SHIFT;
-static_assert(RG_BLOCKS <= SOLO_POOL, "the rows live in the SoloPlan's slot arrays");
 
 // Phase profile of the row engine (MTE_PROFILE device builds, `make prof`): inclusive s_memtime
 // cycles and event counts accumulated in registers and written once per document by finish(), in
@@ -115,10 +116,6 @@ inline u64 g_rg_stats[RS_N + 64];
     } while (0)
 #endif
 
-#ifndef MTE_CPU
-extern __shared__ uint4 g_lds_dyn[];
-#endif
-
 struct RSeg {
     u32 len;
     i32 seq;
@@ -130,22 +127,6 @@ struct RSeg {
     u32 sid;
     u32 props = 0;  // property map id (PROPS engines; 0 = no properties)
     u32 rm2 = 0;    // removers 32..63 (WIDE engines)
-};
-// the extra slot fields of a PROPS engine's rows (the property map id) and of a WIDE one's (removers
-// 32..63); absent otherwise: the lean rows stay eight registers
-template <bool P, bool W>
-struct RowProps {};
-template <>
-struct RowProps<true, false> {
-    simd::V props;
-};
-template <>
-struct RowProps<false, true> {
-    simd::V rm2;
-};
-template <>
-struct RowProps<true, true> {
-    simd::V props, rm2;
 };
 struct RFound {
     bool ok;
@@ -171,11 +152,8 @@ struct RegEngine {
     typedef simd::V V;
     typedef simd::B B;
     static constexpr u32 NBLK = (u32)NR * 8;
-    // One row of slots: vis = (len, seq, rseq, meta), aux = (cap, toff, rm, sid). A live segment has
-    // rm 0, so nodeLength's removal test is one bit test of rm (no separate overlap-set lookup).
-    struct Row : RowProps<PROPS, WIDE> {
-        V len, seq, rseq, meta, cap, toff, rm, sid;
-    };
+    typedef RowStore<NR, PAGED, PROPS, WIDE> Rows;
+    typedef typename Rows::Row Row;
 
     // ---------------------------------------------------------------- state
     simd::VA<RG_LEVELS> LV;  // LV[i] lane j: child count of node j of level i+1 (0 beyond the last)
@@ -234,411 +212,21 @@ struct RegEngine {
     u16* payload;
     u16* arena0;
     u32 seg_cap, arena_cap, payload_len;
-
-    // ---------------------------------------------------------------- slot rows (LDS)
-    // ---------------------------------------------------------------- paged rows
-    V ptab = simd::splat(0);  // lane r: pool row of logical row r (PAGED)
-    u32 n_rows = 0;           // logical rows taken from the pool (PAGED)
-    SD u32 prow(u32 r) const {
-        if constexpr (PAGED) return simd::readlane(ptab, r);
-        else return r;
-    }
+    Rows rows;  // the slot rows (reg_rows.hpp): LDS on the device, arrays in the CPU build
 #ifdef MTE_CPU
-    u32 mem_vis[RG_ROWS * 64][4], mem_aux[RG_ROWS * 64][4];
-    u32 mem_props[RG_ROWS * 64], mem_rm2[RG_ROWS * 64];
-    u64 pool_mask = 0;           // PAGED: pool rows in use (this engine's own pool on the CPU)
-    u32 pool_rows = RG_ROWS, pool_takes = 0;
-    SD u32 pslot(u32 s) const { return PAGED ? prow(s >> 6) * 64 + (s & 63) : s; }
-    SD bool take_row(u32& row) {  // a scattered order, so logical and pool rows differ
-        for (u32 t = 0; t < pool_rows; t++) {
-            const u32 c = (pool_takes * 7 + 3 + t) % pool_rows;
-            if (!((pool_mask >> c) & 1)) {
-                pool_mask |= 1ull << c;
-                pool_takes++;
-                row = c;
-                return true;
-            }
-        }
-        return false;
-    }
-    SD void give_row(u32 row) { pool_mask &= ~(1ull << row); }
-    SD void zero_prow(u32 row) {
-        memset(mem_vis[row * 64], 0, 64 * 16);
-        memset(mem_aux[row * 64], 0, 64 * 16);
-        memset(&mem_props[row * 64], 0, 64 * 4);
-        memset(&mem_rm2[row * 64], 0, 64 * 4);
-    }
-    SD Row ldrow(u32 r) const {
-        Row w;
-        const u32 pr = prow(r);
-        for (u32 l = 0; l < 64; l++) {
-            const u32* v = mem_vis[pr * 64 + l];
-            const u32* a = mem_aux[pr * 64 + l];
-            w.len.x[l] = v[0], w.seq.x[l] = v[1], w.rseq.x[l] = v[2], w.meta.x[l] = v[3];
-            w.cap.x[l] = a[0], w.toff.x[l] = a[1], w.rm.x[l] = a[2], w.sid.x[l] = a[3];
-            if constexpr (PROPS) w.props.x[l] = mem_props[pr * 64 + l];
-            if constexpr (WIDE) w.rm2.x[l] = mem_rm2[pr * 64 + l];
-        }
-        return w;
-    }
-    SD void strow(u32 r, const Row& w) {
-        const u32 pr = prow(r);
-        for (u32 l = 0; l < 64; l++) {
-            u32* v = mem_vis[pr * 64 + l];
-            u32* a = mem_aux[pr * 64 + l];
-            v[0] = w.len.x[l], v[1] = w.seq.x[l], v[2] = w.rseq.x[l], v[3] = w.meta.x[l];
-            a[0] = w.cap.x[l], a[1] = w.toff.x[l], a[2] = w.rm.x[l], a[3] = w.sid.x[l];
-            if constexpr (PROPS) mem_props[pr * 64 + l] = w.props.x[l];
-            if constexpr (WIDE) mem_rm2[pr * 64 + l] = w.rm2.x[l];
-        }
-    }
-    SD V ldf(u32 r, u32 aux, u32 c) const {  // one field of a row
-        V x;
-        const u32 pr = prow(r);
-        for (u32 l = 0; l < 64; l++) x.x[l] = aux ? mem_aux[pr * 64 + l][c] : mem_vis[pr * 64 + l][c];
-        return x;
-    }
-    SD void stf(u32 r, u32 aux, u32 c, V x, B m) {
-        const u32 pr = prow(r);
-        for (u32 l = 0; l < 64; l++)
-            if ((m.m >> l) & 1) (aux ? mem_aux[pr * 64 + l] : mem_vis[pr * 64 + l])[c] = x.x[l];
-    }
-    // slot-index memmove (blocks move as whole 8-slot groups)
-    SD void mv_slots(u32 dst, u32 src, u32 n) {
-        cr = NONE;
-        if (!PAGED) {
-            memmove(mem_vis[dst], mem_vis[src], (size_t)n * 16);
-            memmove(mem_aux[dst], mem_aux[src], (size_t)n * 16);
-            memmove(&mem_props[dst], &mem_props[src], (size_t)n * 4);
-            memmove(&mem_rm2[dst], &mem_rm2[src], (size_t)n * 4);
-            return;
-        }
-        for (u32 t = 0; t < n; t++) {  // slot by slot in the memmove's safe direction
-            const u32 i = dst > src ? n - 1 - t : t;
-            memcpy(mem_vis[pslot(dst + i)], mem_vis[pslot(src + i)], 16);
-            memcpy(mem_aux[pslot(dst + i)], mem_aux[pslot(src + i)], 16);
-            mem_props[pslot(dst + i)] = mem_props[pslot(src + i)];
-            mem_rm2[pslot(dst + i)] = mem_rm2[pslot(src + i)];
-        }
-    }
-    SD void zero_slots(u32 at, u32 n) {
-        cr = NONE;
-        for (u32 i = 0; i < n; i++) {
-            memset(mem_vis[pslot(at + i)], 0, 16);
-            memset(mem_aux[pslot(at + i)], 0, 16);
-            mem_props[pslot(at + i)] = 0;
-            mem_rm2[pslot(at + i)] = 0;
-        }
-    }
-#else
-    // the rows' two LDS arrays (byte offsets into the dynamic LDS): the SoloPlan's slot arrays for
-    // k_solo (so the LDS engine finds them in place after a handoff), a per-wave share for k_rows
-    u32 vbase = (u32)offsetof(SoloPlan, vis), abase = (u32)offsetof(SoloPlan, aux);
-    SD uint4* VISP() const { return reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(g_lds_dyn) + vbase); }
-    SD uint4* AUXP() const { return reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(g_lds_dyn) + abase); }
-    u32 pbase = 0;  // PROPS: byte offset of the slots' property map ids (one u32 per slot)
-    SD u32* PROPP() const { return reinterpret_cast<u32*>(reinterpret_cast<unsigned char*>(g_lds_dyn) + pbase); }
-    u32 r2base = 0;  // WIDE: byte offset of the slots' removers 32..63 (one u32 per slot)
-    SD u32* RM2P() const { return reinterpret_cast<u32*>(reinterpret_cast<unsigned char*>(g_lds_dyn) + r2base); }
-    u32 pool_off = 0;  // PAGED: byte offset of the pool's row mask (ROWS_POOL_WORDS words)
-    SD u32* pool_words() const { return reinterpret_cast<u32*>(reinterpret_cast<unsigned char*>(g_lds_dyn) + pool_off); }
-    SD bool take_row(u32& row) {  // lane 0 claims a free pool row with an LDS atomic or
-        u32 got = NONE;
-        if (__lane_id() == 0) {
-            u32* m = pool_words();
-            for (u32 wd = 0; wd < ROWS_POOL_WORDS && got == NONE; wd++) {
-                u32 cur = __hip_atomic_load(m + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                while (~cur) {
-                    const u32 bit = 1u << __builtin_ctz(~cur);
-                    const u32 old = atomicOr(m + wd, bit);
-                    if (!(old & bit)) {
-                        got = wd * 32 + (u32)__builtin_ctz(bit);
-                        break;
-                    }
-                    cur = old | bit;
-                }
-            }
-        }
-        got = simd::readlane(simd::V{got}, 0);
-        row = got;
-        return got != NONE;
-    }
-    // A full pool is usually full for a moment (the other waves' documents shrink and end all the
-    // time): wait up to ~4 ms for a row before giving the document up (a bounded wait, so waves
-    // that all wait cannot deadlock: they spill; ~0.4 ms still let one C2 document in five steps
-    // spill into a 100 ms HBM re-run).
-    SD bool take_row_wait(u32& row) {
-        for (u32 t = 0; t < ROWS_WAIT_TRIES; t++) {
-            if (take_row(row)) return true;
-            __builtin_amdgcn_s_sleep(8);  // ~512 cycles
-        }
-        return take_row(row);
-    }
-    SD void give_row(u32 row) {
-        if (__lane_id() == 0) atomicAnd(pool_words() + (row >> 5), ~(1u << (row & 31)));
-    }
-    SD void zero_prow(u32 row) {
-        VISP()[row * 64 + __lane_id()] = make_uint4(0, 0, 0, 0);
-        AUXP()[row * 64 + __lane_id()] = make_uint4(0, 0, 0, 0);
-        if constexpr (PROPS) PROPP()[row * 64 + __lane_id()] = 0u;
-        if constexpr (WIDE) RM2P()[row * 64 + __lane_id()] = 0u;
-        simd::lds_order();
-    }
-    // physical slot of logical slot s, per lane (PAGED: a block range can cross pool rows)
-    SD u32 pslot(u32 s) const {
-        if constexpr (PAGED) return simd::bperm(ptab, simd::V{s >> 6}).x * 64u + (s & 63u);
-        else return s;
-    }
-    SD Row ldrow(u32 r) const {
-        const u32 i = prow(r) * 64 + __lane_id();
-        const uint4 v = VISP()[i], a = AUXP()[i];
-        Row w;
-        w.len = V{v.x}, w.seq = V{v.y}, w.rseq = V{v.z}, w.meta = V{v.w};
-        w.cap = V{a.x}, w.toff = V{a.y}, w.rm = V{a.z}, w.sid = V{a.w};
-        if constexpr (PROPS) w.props = V{PROPP()[i]};
-        if constexpr (WIDE) w.rm2 = V{RM2P()[i]};
-        return w;
-    }
-    SD void strow(u32 r, const Row& w) {
-        const u32 i = prow(r) * 64 + __lane_id();
-        VISP()[i] = make_uint4(w.len.x, w.seq.x, w.rseq.x, w.meta.x);
-        AUXP()[i] = make_uint4(w.cap.x, w.toff.x, w.rm.x, w.sid.x);
-        if constexpr (PROPS) PROPP()[i] = w.props.x;
-        if constexpr (WIDE) RM2P()[i] = w.rm2.x;
-        simd::lds_order();
-    }
-    SD V ldf(u32 r, u32 aux, u32 c) const {
-        const u32* b = reinterpret_cast<const u32*>(aux ? AUXP() : VISP());
-        return V{b[(prow(r) * 64 + __lane_id()) * 4 + c]};
-    }
-    SD void stf(u32 r, u32 aux, u32 c, V x, B m) {
-        u32* b = reinterpret_cast<u32*>(aux ? AUXP() : VISP());
-        if (simd::lane_of(m)) b[(prow(r) * 64 + __lane_id()) * 4 + c] = x.x;
-        simd::lds_order();
-    }
-    // Overlapping slot move, one 64-slot chunk per LDS round trip; the lean engines overlap each
-    // chunk's writes with the next chunk's reads (-0.3 % on the lone 10^6-op document, profiles/r05/
-    // r05x). (Issuing eight chunks' reads before their writes measured 7 % SLOWER: 4.25 vs 3.93 us/op.)
-    SD void mv_slots(u32 dst, u32 src, u32 n) {
-        cr = NONE;
-        uint4* V4 = VISP();
-        uint4* A4 = AUXP();
-        const u32 L = __lane_id();
-        if constexpr (PAGED) {  // the same chunks, each lane's slots mapped through ptab
-            const bool up = dst > src;
-            for (u32 c = 0; c < n; c += 64) {
-                const i32 i = up ? (i32)(n - c) - 64 + (i32)L : (i32)(c + L);
-                const bool ok = i >= 0 && (u32)i < n;
-                const u32 ii = ok ? (u32)i : 0u;
-                const u32 ps = pslot(src + ii), pd = pslot(dst + ii);
-                uint4 v = make_uint4(0, 0, 0, 0), a = v;
-                u32 pp = 0, q2 = 0;
-                if (ok) {
-                    v = V4[ps];
-                    a = A4[ps];
-                    if constexpr (PROPS) pp = PROPP()[ps];
-                    if constexpr (WIDE) q2 = RM2P()[ps];
-                }
-                simd::lds_order();
-                if (ok) {
-                    V4[pd] = v;
-                    A4[pd] = a;
-                    if constexpr (PROPS) PROPP()[pd] = pp;
-                    if constexpr (WIDE) RM2P()[pd] = q2;
-                }
-                simd::lds_order();
-            }
-            return;
-        }
-        if constexpr (!PROPS && !WIDE) {
-            // two stages: the next chunk's reads go out before this chunk's writes. The ranges never
-            // meet: the walk runs away from the destination (down the slots when moving up, up them
-            // when moving down), so every read still sees the slots before the move.
-            const uint4 z = make_uint4(0, 0, 0, 0);
-            if (dst > src) {
-                i32 i = (i32)n - 64 + (i32)L;
-                uint4 v = z, a = z;
-                if (i >= 0) {
-                    v = V4[src + (u32)i];
-                    a = A4[src + (u32)i];
-                }
-                for (i32 b = (i32)n - 64; b > -64; b -= 64) {
-                    const i32 j = i - 64;
-                    uint4 v2 = z, a2 = z;
-                    if (b - 64 > -64 && j >= 0) {
-                        v2 = V4[src + (u32)j];
-                        a2 = A4[src + (u32)j];
-                    }
-                    simd::lds_order();
-                    if (i >= 0) {
-                        V4[dst + (u32)i] = v;
-                        A4[dst + (u32)i] = a;
-                    }
-                    simd::lds_order();
-                    v = v2;
-                    a = a2;
-                    i = j;
-                }
-            } else {
-                u32 i = L;
-                uint4 v = z, a = z;
-                if (i < n) {
-                    v = V4[src + i];
-                    a = A4[src + i];
-                }
-                for (u32 b = 0; b < n; b += 64) {
-                    const u32 j = i + 64;
-                    uint4 v2 = z, a2 = z;
-                    if (b + 64 < n && j < n) {
-                        v2 = V4[src + j];
-                        a2 = A4[src + j];
-                    }
-                    simd::lds_order();
-                    if (i < n) {
-                        V4[dst + i] = v;
-                        A4[dst + i] = a;
-                    }
-                    simd::lds_order();
-                    v = v2;
-                    a = a2;
-                    i = j;
-                }
-            }
-            return;
-        }
-        if (dst > src) {
-            for (i32 b = (i32)n - 64; b > -64; b -= 64) {
-                const i32 i = b + (i32)L;
-                uint4 v = make_uint4(0, 0, 0, 0), a = v;
-                u32 pp = 0, q2 = 0;
-                if (i >= 0) {
-                    v = V4[src + (u32)i];
-                    a = A4[src + (u32)i];
-                    if constexpr (PROPS) pp = PROPP()[src + (u32)i];
-                    if constexpr (WIDE) q2 = RM2P()[src + (u32)i];
-                }
-                simd::lds_order();
-                if (i >= 0) {
-                    V4[dst + (u32)i] = v;
-                    A4[dst + (u32)i] = a;
-                    if constexpr (PROPS) PROPP()[dst + (u32)i] = pp;
-                    if constexpr (WIDE) RM2P()[dst + (u32)i] = q2;
-                }
-                simd::lds_order();
-            }
-        } else {
-            for (u32 b = 0; b < n; b += 64) {
-                const u32 i = b + L;
-                uint4 v = make_uint4(0, 0, 0, 0), a = v;
-                u32 pp = 0, q2 = 0;
-                if (i < n) {
-                    v = V4[src + i];
-                    a = A4[src + i];
-                    if constexpr (PROPS) pp = PROPP()[src + i];
-                    if constexpr (WIDE) q2 = RM2P()[src + i];
-                }
-                simd::lds_order();
-                if (i < n) {
-                    V4[dst + i] = v;
-                    A4[dst + i] = a;
-                    if constexpr (PROPS) PROPP()[dst + i] = pp;
-                    if constexpr (WIDE) RM2P()[dst + i] = q2;
-                }
-                simd::lds_order();
-            }
-        }
-    }
-    SD void zero_slots(u32 at, u32 n) {
-        cr = NONE;
-        if constexpr (!PAGED && !PROPS && !WIDE) {
-            for (u32 b = __lane_id(); b < n; b += 64) {
-                VISP()[at + b] = make_uint4(0, 0, 0, 0);
-                AUXP()[at + b] = make_uint4(0, 0, 0, 0);
-            }
-            simd::lds_order();
-            return;
-        }
-        for (u32 c = 0; c < n; c += 64) {
-            const u32 b = c + __lane_id();
-            const u32 ps = pslot(at + (b < n ? b : 0u));
-            if (b < n) {
-                VISP()[ps] = make_uint4(0, 0, 0, 0);
-                AUXP()[ps] = make_uint4(0, 0, 0, 0);
-                if constexpr (PROPS) PROPP()[ps] = 0u;
-                if constexpr (WIDE) RM2P()[ps] = 0u;
-            }
-        }
-        simd::lds_order();
-    }
+    u32& pool_rows = rows.at.pool_rows;  // the CPU pool's size, where tests/native/reg_cpu.cpp sets it
 #endif
-    SD V ld_len(u32 r) const { return ldf(r, 0, 0); }
-    SD V ld_meta(u32 r) const { return ldf(r, 0, 3); }
-    SD V ld_sid(u32 r) const { return ldf(r, 1, 3); }
-    // The row an op is working on stays in registers between its steps (resolve -> split -> insert ->
-    // LRU; heap pop -> scour -> needsScour): row(r) reads LDS only when r is not the cached row,
-    // putrow writes through. Anything that moves blocks (mv_slots / zero_slots) drops the cache.
-    Row cw;
-    u32 cr = NONE;
-    SD Row row(u32 r) {
-        if (r != cr) {
-            cw = ldrow(r);
-            cr = r;
-        }
-        return cw;
-    }
-    SD void putrow(u32 r, const Row& w) {
-        strow(r, w);
-        cw = w;
-        cr = r;
-    }
-    // the cached row itself, for edits in place (no working copy of its eight registers); pair with
-    // writeback(r) before anything else touches the cache
-    SD Row& rowref(u32 r) {
-        if (r != cr) {
-            cw = ldrow(r);
-            cr = r;
-        }
-        return cw;
-    }
-    SD void writeback(u32 r) { strow(r, cw); }
+    // a PAGED engine's rows back to the pool, when it is done with its document
+    SD void release_rows() { rows.release_rows(); }
 
-    // PAGED: logical rows [n_rows, need) from the pool, zeroed (rows past the last block stay zero)
-    bool pool_full = false;  // PAGED: the last grow found the pool full (not the logical row limit)
-    SD bool grow_rows(u32 need) {
-        while (n_rows < need) {
-            u32 row;
-#ifdef MTE_CPU
-            if (n_rows >= (u32)NR || !take_row(row)) return false;
-#else
-            if (n_rows >= (u32)NR) return false;
-            if (!take_row_wait(row)) {
-                pool_full = true;
-                return false;
-            }
-#endif
-            zero_prow(row);
-            ptab = simd::writelane(ptab, n_rows, row);
-            n_rows++;
-        }
-        return true;
-    }
-    SD void shrink_rows(u32 keep) {
-        cr = NONE;
-        while (n_rows > keep) give_row(prow(--n_rows));
-    }
-    SD void release_rows() {
-        if constexpr (PAGED) shrink_rows(0);
-    }
-    // every row the state uses is held (a PAGED engine whose first row the pool never gave has none)
-    SD bool rows_whole() const {
-        if constexpr (PAGED) return n_rows * 8 >= n_lb;
-        else return true;
-    }
+    SD V ld_len(u32 r) const { return rows.ldf(r, 0, 0); }
+    SD V ld_meta(u32 r) const { return rows.ldf(r, 0, 3); }
+    SD V ld_sid(u32 r) const { return rows.ldf(r, 1, 3); }
     // Room for leaf blocks [0, nb): PAGED takes pool rows (none left: spill the document, the host
     // re-runs it); otherwise the fixed rows must hold them.
     SD bool ensure_blocks(u32 nb) {
         if constexpr (PAGED) {
-            if (grow_rows((nb + 7) >> 3)) return true;
+            if (rows.grow_rows((nb + 7) >> 3)) return true;
             fail(REG_HANDOFF, curSeq);
         } else {
             if (nb <= NBLK) return true;
@@ -647,21 +235,12 @@ struct RegEngine {
         return false;
     }
 
-    SD RegEngine(const Params& p_, u32 doc_) : p(p_), doc(doc_) { setup(); }
-#ifndef MTE_CPU
-    // rows in another LDS region (k_rows: one share of the CU's LDS per wave)
-    SD RegEngine(const Params& p_, u32 doc_, u32 vb, u32 ab, u32 mode, u32 pool = 0, u32 pb = 0, u32 r2b = 0)
-        : p(p_), doc(doc_) {
-        vbase = vb;
-        abase = ab;
-        pbase = pb;
-        r2base = r2b;
-        pool_off = pool;
-        res_mode = mode;
+    // g: where the rows are (lean k_solo's place unless told otherwise)
+    SD RegEngine(const Params& p_, u32 doc_, const RowsLds& g = RowsLds::solo_lean())
+        : p(p_), doc(doc_), rows(g), res_mode(g.mode) {
         setup();
     }
-#endif
-    u32 res_mode = 4;  // DocRes::mode of a document this engine finishes (4: k_solo, 5: k_rows)
+    u32 res_mode;  // DocRes::mode of a document this engine finishes (4: k_solo, 5: k_rows)
     SD void setup() {
         const DocCfg& c = p.docs[doc];
         payload = p.payload + c.payload_off;
@@ -685,16 +264,6 @@ struct RegEngine {
     // table, immutable once built; id 0 = no properties. Lane i holds pair i.
     u32* maps = nullptr;
     u32 map_cap = 0, mw = 0, mapNext = 1;
-    // lanes below each lane set in m (mbcnt)
-    SD static V rank_below(u64 m) {
-#ifdef MTE_CPU
-        V r;
-        for (u32 l = 0; l < 64; l++) r.x[l] = (u32)__builtin_popcountll(m & ((1ull << l) - 1ull));
-        return r;
-#else
-        return V{__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u))};
-#endif
-    }
     // matchProperties on one value, b uniform (properties.ts:72-80): equal ids, or b an object value
     // that a's deep-equality bits name
     SD B val_match(V a, u32 b) const {
@@ -756,7 +325,7 @@ struct RegEngine {
             keep = keep & (L() < n);
             const u64 km = simd::ballot(keep);
             const u32 nk = (u32)__builtin_popcountll(km);
-            const V below = rank_below(km);
+            const V below = simd::rank_below(km);
             const V dst = simd::sel(keep, below, (L() - below) + nk);  // a permutation of the lanes
             K = simd::push(K, dst);
             Vv = simd::push(Vv, dst);
@@ -796,10 +365,9 @@ struct RegEngine {
     }
     SD void init() {
         if constexpr (PAGED) {
-            n_rows = 0;
-            ptab = simd::splat(0);
+            rows.reset_rows();
         } else {
-            zero_slots(0, NBLK * 8);  // every slot empty: rows past the last block stay zero
+            rows.zero_slots(0, NBLK * 8);  // every slot empty: rows past the last block stay zero
         }
         LV.zero();
         HK.zero();
@@ -820,7 +388,7 @@ struct RegEngine {
         for (u32 i = 0; i < RP_N; i++) pf[i] = 0;
 #endif
         if constexpr (PAGED)
-            if (!grow_rows(1)) status = REG_HANDOFF;
+            if (!rows.grow_rows(1)) status = REG_HANDOFF;
     }
 
     SD static V L() { return simd::lanes(); }
@@ -851,11 +419,11 @@ struct RegEngine {
     SD static u32 count_in(const Row& w, u32 k) { return (u32)__builtin_popcount(group_bits(simd::ballot(w.len != 0u), k)); }
     SD static u32 ns_in(const Row& w, u32 k) { return (simd::readlane(w.meta, gbase(k)) >> NS_SHIFT) & 3u; }
     SD static void ns_put(Row& w, u32 k, u32 sc) { w.meta = simd::sel(in_group(k), (w.meta & ~NS_MASK) | (sc << NS_SHIFT), w.meta); }
-    SD u32 count(u32 k) { return count_in(row(k >> 3), k); }
-    SD u32 ns_get(u32 k) { return ns_in(row(k >> 3), k); }
+    SD u32 count(u32 k) { return count_in(rows.row(k >> 3), k); }
+    SD u32 ns_get(u32 k) { return ns_in(rows.row(k >> 3), k); }
     SD void ns_set(u32 k, u32 sc) {
-        ns_put(rowref(k >> 3), k, sc);
-        writeback(k >> 3);
+        ns_put(rows.rowref(k >> 3), k, sc);
+        rows.writeback(k >> 3);
     }
 
     // nodeLength of every slot of a row for (refSeq R, client C) (mergeTree.ts:1659-1699):
@@ -906,8 +474,7 @@ struct RegEngine {
             f.cnt = (u32)__builtin_popcount(group_bits(simd::ballot(valid), k));
             f.row = r;
             f.carry = carry;
-            cw = w;
-            cr = r;
+            rows.cache(r, w);
             if (cm) {
                 const u32 l = (u32)__builtin_ctzll(cm);
                 f.slot = (i32)(l - gb);
@@ -918,13 +485,13 @@ struct RegEngine {
         // two row buffers, each refilled (unconditionally: the last row again at the end, so the
         // LDS counter wait stays exact) while the other one is scanned; the loop only finds the hit
         // row (no state written in it, so no per-row register copies)
-        Row a = row(r0), b;
+        Row a = rows.row(r0), b;
         V v, incl;
         u64 hit = 0;
         bool inb = false;
         u32 r = r0;
         for (;;) {
-            b = ldrow(r + 1 < last ? r + 1 : last);
+            b = rows.ldrow(r + 1 < last ? r + 1 : last);
             RG_COUNT(RP_N_RESOLVE, 1);
             v = vis(a, R, C);
             RG_STAT(RS_RES_ROWS, 1);
@@ -933,7 +500,7 @@ struct RegEngine {
             if (hit) break;
             carry = simd::readlane(incl, 63);
             if (++r >= nrows) break;
-            a = ldrow(r + 1 < last ? r + 1 : last);
+            a = rows.ldrow(r + 1 < last ? r + 1 : last);
             RG_COUNT(RP_N_RESOLVE, 1);
             v = vis(b, R, C);
             RG_STAT(RS_RES_ROWS, 1);
@@ -1000,10 +567,10 @@ struct RegEngine {
         const u32 n = (n_lb - from) * 8;
         RG_STAT(RS_MOVE_SLOTS, n);
         if (d > 0) {
-            mv_slots((from + (u32)d) * 8, from * 8, n);
+            rows.mv_slots((from + (u32)d) * 8, from * 8, n);
         } else {
-            mv_slots((from - (u32)(-d)) * 8, from * 8, n);
-            zero_slots((n_lb - (u32)(-d)) * 8, (u32)(-d) * 8);
+            rows.mv_slots((from - (u32)(-d)) * 8, from * 8, n);
+            rows.zero_slots((n_lb - (u32)(-d)) * 8, (u32)(-d) * 8);
         }
     }
 
@@ -1017,7 +584,7 @@ struct RegEngine {
             return NONE;
         }
         const u32 r = k >> 3, gb = gbase(k);
-        Row& w = rowref(r);
+        Row& w = rows.rowref(r);
         const V sl = L() & 7u;
         const B ing = in_group(k);
         const B mv = ing & (sl > j);
@@ -1042,7 +609,7 @@ struct RegEngine {
         put(w.sid, rec.sid);
         if constexpr (PROPS) put(w.props, rec.props);
         if constexpr (WIDE) put(w.rm2, rec.rm2);
-        writeback(r);
+        rows.writeback(r);
         if (cnt + 1 < 8) return k;
         split_block(k);
         return j < 4 ? k : k + 1;
@@ -1058,9 +625,9 @@ struct RegEngine {
         const V sl = L() & 7u;
         const B lo = in_group(k + 1) & (sl < 4u), hi2 = in_group(k + 1) & (sl >= 4u), hi = in_group(k) & (sl >= 4u);
         const V src = (L() + (r2 == r ? 0u : 64u) - 4u) & 63u;  // new slot s <- old slot 4+s of block k
-        Row w = row(r);
+        Row w = rows.row(r);
         const u32 nsk = simd::readlane(w.meta, gbase(k)) & NS_MASK;
-        Row w2 = r2 == r ? w : ldrow(r2);
+        Row w2 = r2 == r ? w : rows.ldrow(r2);
         auto mv = [&](V& x, V& y, u32 keepHi) MTE_LI {  // x: row r, y: row r2
             const V moved = simd::bperm(x, src);
             if (r2 == r) {
@@ -1085,11 +652,11 @@ struct RegEngine {
         // the new block's needsScour is undefined
         if (r2 == r) {
             w.meta = simd::sel(in_group(k + 1), w.meta & ~NS_MASK, w.meta);
-            putrow(r, w);
+            rows.putrow(r, w);
         } else {
             w2.meta = simd::sel(in_group(k + 1), w2.meta & ~NS_MASK, w2.meta);
-            strow(r2, w2);
-            putrow(r, w);
+            rows.strow(r2, w2);
+            rows.putrow(r, w);
         }
         n_lb++;
         if (n_lb > max_lb) max_lb = n_lb;
@@ -1330,7 +897,7 @@ struct RegEngine {
         u32 top = 0;
         for (u32 k = 0; k < n_lb; k++) {
             const u32 r = k >> 3, gb = gbase(k);
-            Row w = ldrow(r);
+            Row w = rows.ldrow(r);
             const u32 cnt = (u32)__builtin_popcount(group_bits(simd::ballot(w.len != 0u), k));
             bool dirty = false;
             for (u32 s = 0; s < cnt; s++) {
@@ -1350,7 +917,7 @@ struct RegEngine {
                 dirty = true;
                 top += cap;
             }
-            if (dirty) putrow(r, w);
+            if (dirty) rows.putrow(r, w);
         }
         simd::wave_fence();
         arenaSel = other;
@@ -1380,7 +947,7 @@ struct RegEngine {
         if (cnt > 8) cnt = 8;
         const u32 r = k >> 3, gb = gbase(k);
         const B ing = in_group(k);
-        Row w = row(r);
+        Row w = rows.row(r);
         const B act = ing & (w.len != 0u);
         const B rem = act & (w.rseq != RSEQ_LIVE);
         const u32 mDROP = group_bits(simd::ballot(rem & simd::sle(w.rseq, minSeq)), k);
@@ -1458,7 +1025,7 @@ struct RegEngine {
             }
             arena_gc();  // moves every arena text: re-read the slots and redo the runs
             if (status) return cnt;
-            w = row(r);
+            w = rows.row(r);
             fence_arena();
         }
         copy_runs(jdst, jsrc, jlen);
@@ -1487,7 +1054,7 @@ struct RegEngine {
         if constexpr (PROPS) cmp(w.props, 0u);
         if constexpr (WIDE) cmp(w.rm2, 0u);
         ns_put(w, k, SC_FALSE);  // scourNode's caller clears needsScour (mergeTree.ts:1457): same write
-        putrow(r, w);
+        rows.putrow(r, w);
         scoured = true;
         return nkeep;
     }
@@ -1524,7 +1091,7 @@ struct RegEngine {
         fence_arena();
         const u32 r = k >> 3, gb = gbase(k);
         const B ing = in_group(k);
-        Row w = row(r);
+        Row w = rows.row(r);
         const B act = ing & (w.len != 0u);
         const B rem = act & (w.rseq != RSEQ_LIVE);
         const u32 mREM = group_bits(simd::ballot(rem), k);
@@ -1623,7 +1190,7 @@ struct RegEngine {
             }
             arena_gc();  // moves every arena text: re-read the slots and redo the chain
             if (status) return cnt;
-            w = row(r);
+            w = rows.row(r);
         }
         if (jn) run_jobs(jn, jdst, jsrc, jlen);
         // compaction: group lane gb+i takes kept slot i
@@ -1645,7 +1212,7 @@ struct RegEngine {
         if constexpr (PROPS) cmp(w.props, nullptr, 0u);
         if constexpr (WIDE) cmp(w.rm2, nullptr, 0u);
         ns_put(w, k, SC_FALSE);
-        putrow(r, w);
+        rows.putrow(r, w);
         scoured = true;
         return nkeep;
     }
@@ -1694,7 +1261,7 @@ struct RegEngine {
         const V sg = (sib + k0) * 8u + q;  // source slot (global)
         const u32 r0 = k0 >> 3, r1 = r0 + 1 < (u32)NR ? r0 + 1 : r0;
         const B inr0 = (sg >> 6) == r0;
-        Row a = ldrow(r0), b = ldrow(r1);
+        Row a = rows.ldrow(r0), b = rows.ldrow(r1);
         auto gather = [&](const V& x0, const V& x1) MTE_LI {
             return simd::sel(inr0, simd::bperm(x0, sg & 63u), simd::bperm(x1, sg & 63u));
         };
@@ -1722,7 +1289,7 @@ struct RegEngine {
             const V nB = simd::sel(dj < extra, base + 1, simd::splat(base));
             const B have = inb & (dq < nB);
             const V ti = (dj * base + big + dq) & 63u;
-            Row w = ldrow(rr);
+            Row w = rows.ldrow(rr);
             auto put = [&](V& x, const V& tv) MTE_LI { x = simd::sel(have, simd::bperm(tv, ti), simd::sel(inb, 0u, x)); };
             put(w.len, t.len);
             put(w.seq, t.seq);
@@ -1734,9 +1301,9 @@ struct RegEngine {
             put(w.sid, t.sid);
             if constexpr (PROPS) put(w.props, t.props);
             if constexpr (WIDE) put(w.rm2, t.rm2);
-            strow(rr, w);
+            rows.strow(rr, w);
         }
-        cr = NONE;
+        rows.drop_row();
         n_lb = (u32)((i32)n_lb + d);
         if (n_lb > max_lb) max_lb = n_lb;
         LV.set(0, simd::writelane(LV.get(0), pi, kk));
@@ -1815,7 +1382,7 @@ struct RegEngine {
         RG_PROF(RP_SPLIT_AT);
         RG_STAT(RS_SPLIT_AT, 1);
         const u32 r = f.k >> 3, l = gbase(f.k) + (u32)f.slot;
-        const Row w = row(r);
+        const Row w = rows.row(r);
         RSeg t;
         t.len = simd::readlane(w.len, l);
         t.seq = (i32)simd::readlane(w.seq, l);
@@ -1897,7 +1464,7 @@ struct RegEngine {
         u32 carry = c1;
         const u32 cbit = WIDE ? 1u << (C & 31u) : 1u << C;
         for (u32 r = r1; r < nrows && (i32)carry < p2; r++) {
-            Row& w = rowref(r);
+            Row& w = rows.rowref(r);
             const V v = vis(w, R, C);
             const V incl = simd::scan_incl(v) + carry;
             const V ex = incl - v;
@@ -1914,7 +1481,7 @@ struct RegEngine {
             }
             w.meta = simd::sel(was, w.meta | F_OVL, simd::sel(fresh, (w.meta & ~0xFF00u) | (C << 8) | F_REMOVED, w.meta));
             w.rseq = simd::sel(fresh, (u32)seq, w.rseq);
-            writeback(r);
+            rows.writeback(r);
             // addToLRUSet per block, document order: the first marked slot of each block
             for (u64 gm = mm; gm;) {
                 const u32 l = (u32)__builtin_ctzll(gm);
@@ -1946,7 +1513,7 @@ struct RegEngine {
         const u32 nrows = (n_lb + 7) >> 3;
         u32 carry = c1, memoOld = NONE, memoNew = 0;
         for (u32 r = r1; r < nrows && (i32)carry < p2; r++) {
-            Row& w = rowref(r);
+            Row& w = rows.rowref(r);
             const V v = vis(w, R, C);
             const V incl = simd::scan_incl(v) + carry;
             const V ex = incl - v;
@@ -1969,7 +1536,7 @@ struct RegEngine {
                 w.props = simd::sel(same, nid, w.props);
                 pending &= ~simd::ballot(same);
             }
-            writeback(r);
+            rows.writeback(r);
             for (u64 gm = mm; gm;) {  // addToLRUSet per block, document order
                 const u32 l = (u32)__builtin_ctzll(gm);
                 const u32 g = l >> 3;
@@ -1991,7 +1558,7 @@ struct RegEngine {
             // the last block's row go back at once (a spare per wave, twelve per CU, had made the
             // pool run out on C2's peaks)
             const u32 keep = (n_lb + 7) >> 3;
-            if (n_rows > keep) shrink_rows(keep);
+            if (rows.n_rows > keep) rows.shrink_rows(keep);
             return n_lb + 4 <= lb_lim && heapSize + n_lb + 8 < RG_HEAP && height + 2 <= RG_LEVELS &&
                    (n_lb < 57 || simd::readlane(LV.get(0), 56) == 0u);
         }
@@ -2089,20 +1656,16 @@ struct RegEngine {
         // newest load outstanding there must be an op old. (Loading before the decode, or a
         // four-register ring indexed by a switch, made every chunk wait for a fresh HBM load.)
         V CUR = load_chunk(0), NXT = load_chunk(8);
-#ifndef MTE_CPU
         // wait for the first chunk here, once: CUR then enters the loop with no load outstanding, so
         // the decodes need no vector-memory wait at all (stores of the merge arena included)
-        asm volatile("" ::"v"(CUR.x));
-#endif
+        simd::wait_loaded(CUR);
         u32 k = 0;
         for (; k < n && !status; k++) {
             const u32 r = k & 7u;
             const bool first = r == 0 && k != 0;
             if (first) {
                 CUR = NXT;
-#ifndef MTE_CPU
-                asm volatile("");  // keep this a branch: a select would read NXT (and wait) every op
-#endif
+                simd::keep_branch();  // keep this a branch: a select would read NXT (and wait) every op
             }
             mte_op op;
             {
@@ -2125,29 +1688,6 @@ struct RegEngine {
     // The final segments in document order (walkAllSegments, mergeTree.ts:2969-2983) in the LDS
     // engine's row format (removedSeq 0 and removedClient 0 for live segments), text gathered into
     // the document's run of the output text pool, and the per-document result record.
-    SD u32 atomic_reserve(u32* ctr, u32 n) const {
-#ifdef MTE_CPU
-        const u32 o = *ctr;
-        *ctr += n;
-        return o;
-#else
-        u32 o = 0;
-        if (simd::lane0()) o = atomicAdd(ctr, n);
-        return __builtin_amdgcn_readfirstlane(o);
-#endif
-    }
-    SD u64 atomic_reserve64(u64* ctr, u64 n) const {
-#ifdef MTE_CPU
-        const u64 o = *ctr;
-        *ctr += n;
-        return o;
-#else
-        u64 o = 0;
-        if (simd::lane0()) o = atomicAdd((unsigned long long*)ctr, (unsigned long long)n);
-        const u32 lo = __builtin_amdgcn_readfirstlane((u32)o), hi = __builtin_amdgcn_readfirstlane((u32)(o >> 32));
-        return ((u64)hi << 32) | lo;
-#endif
-    }
     // the document leaves this engine unfinished (k_rows has no LDS plan to hand it to): the host
     // re-runs it HBM-resident from its first op (engine.hpp mark_spilled)
     SD void mark_spilled() {
@@ -2160,9 +1700,7 @@ struct RegEngine {
             o.max_lb = max_lb;
             o.mode = 0;
             o.spill_why = (n_lb << 8) | (heapSize << 20);
-#ifndef MTE_CPU
-            atomicAdd(&p.counters[2], 1u);
-#endif
+            simd::count_add(&p.counters[2], 1u);
         }
     }
     SD void finish() {
@@ -2177,8 +1715,8 @@ struct RegEngine {
         }
         u32 off = 0, toff = 0;
         if (status == 0) {
-            off = atomic_reserve(&p.counters[1], nseg);
-            toff = (u32)atomic_reserve64((u64*)&p.counters[6], ntext);
+            off = simd::reserve(&p.counters[1], nseg);
+            toff = (u32)simd::reserve((u64*)&p.counters[6], (u64)ntext);
             if ((u64)off + nseg > p.out_cap || (u64)toff + ntext > p.out_text_cap) {
                 fail(MTE_DOC_CAPACITY, curSeq);
                 nseg = 0;
@@ -2193,7 +1731,7 @@ struct RegEngine {
             u32* oa = (u32*)p.out_aux;
             u32* oo = (u32*)p.out_ovl;
             for (u32 r = 0; r < nrows; r++) {
-                const Row w = ldrow(r);
+                const Row w = rows.ldrow(r);
                 const B have = w.len != 0u;
                 const B txt = have & ((w.meta & F_MARKER) == 0u);
                 const V one = simd::sel(have, 1u, simd::splat(0));
@@ -2287,6 +1825,99 @@ struct RegEngine {
 #endif
     }
 
+    // ---------------------------------------------------------------- the stored state
+    // A replay state outside its engine -- a checkpoint (below), or the dump of a k_rows document that
+    // continues HBM-resident in the same pass -- is made of three parts, each written down once here:
+    //   a row:     its fields in Row::fields order, 64 words (one per lane) each;
+    //   registers: LV, HK and HS, 8 registers of 64 words each (RG_STATE_REGS);
+    //   scalars:   the ST_* list, scalar i in lane i of one V (lanes below ST_BASE are the user's).
+    enum : u32 { ST_BASE = 4, ST_NLB = ST_BASE, ST_HEIGHT, ST_HEAPSIZE, ST_HEAPTOP, ST_MINSEQ, ST_CURSEQ, ST_SEGNEXT,
+                 ST_ARENATOP, ST_ARENASEL, ST_MAPNEXT, ST_NOPS, ST_NMSGS, ST_NGC, ST_MAXLB, ST_END };
+    static constexpr u32 NF = Row::NF;
+    static_assert(3 * RG_LEVELS == RG_STATE_REGS, "LV, HK, HS");
+    SD static void put_row(u32* o, const Row& w) {
+        u32 i = 0;
+        w.for_each_field([&](u32, const V& x) MTE_LI { simd::st(o + 64 * i++, L(), x, simd::mk_all()); });
+    }
+    // a row stored by an engine with (sp, sw) for (PROPS, WIDE); a field it did not have is 0
+    SD static Row get_row(const u32* o, bool sp = PROPS, bool sw = WIDE) {
+        Row w;
+        u32 i = 0;
+        w.for_each_field([&](u32 id, V& x) MTE_LI {
+            const bool has = id < Row::FID_PROPS || (id == Row::FID_PROPS ? sp : sw);
+            x = has ? simd::ld(o + 64 * i, L(), simd::mk_all()) : simd::splat(0);
+            i += has;
+        });
+        return w;
+    }
+    SD void put_regs(u32* g) const {
+#pragma unroll
+        for (u32 i = 0; i < 8; i++) {
+            simd::st(g + 64 * i, L(), LV.get(i), simd::mk_all());
+            simd::st(g + 64 * (8 + i), L(), HK.get(i), simd::mk_all());
+            simd::st(g + 64 * (16 + i), L(), HS.get(i), simd::mk_all());
+        }
+    }
+    SD void get_regs(const u32* g) {
+#pragma unroll
+        for (u32 i = 0; i < 8; i++) {
+            LV.set(i, simd::ld(g + 64 * i, L(), simd::mk_all()));
+            HK.set(i, simd::ld(g + 64 * (8 + i), L(), simd::mk_all()));
+            HS.set(i, simd::ld(g + 64 * (16 + i), L(), simd::mk_all()));
+        }
+    }
+    SD V scalars() const {
+        const u32 sv[ST_END - ST_BASE] = {n_lb, height, heapSize, (u32)heapTop, (u32)minSeq, (u32)curSeq, segNext,
+                                          arenaTop, arenaSel, PROPS ? mapNext : 1u, ops_n(), msgs_n(), n_gc, max_lb};
+        V h = simd::splat(0);
+        for (u32 i = ST_BASE; i < ST_END; i++) h = simd::sel(L() == i, sv[i - ST_BASE], h);
+        return h;
+    }
+    SD void set_scalars(V h) {
+        auto hw = [&](u32 i) MTE_LI { return simd::readlane(h, i); };
+        n_lb = hw(ST_NLB);
+        height = hw(ST_HEIGHT);
+        heapSize = hw(ST_HEAPSIZE);
+        heapTop = (i32)hw(ST_HEAPTOP);
+        minSeq = (i32)hw(ST_MINSEQ);
+        curSeq = (i32)hw(ST_CURSEQ);
+        segNext = hw(ST_SEGNEXT);
+        arenaTop = hw(ST_ARENATOP);
+        arenaSel = hw(ST_ARENASEL) & 1u;
+        mapNext = hw(ST_MAPNEXT);
+        set_counts(hw(ST_NOPS), hw(ST_NMSGS));
+        n_gc = hw(ST_NGC);
+        max_lb = hw(ST_MAXLB);
+    }
+
+    // The dump (k_rows' rows_dump -> k_rows_cont, mte_solo.hip): in the document's HBM slot logical row
+    // rr at word rr * NF * 64 and the registers at the fixed word DUMP_REGS; in its queue record
+    // (ROWS_CONT_WORDS words) doc, slot, op index (lo, hi), then the scalars. The merge arena and the
+    // map table stay where they are: the same pass goes on using them.
+    static constexpr u32 DUMP_REGS = (u32)RG_ROWS * NF * 64;
+    static constexpr u64 DUMP_BYTES = (u64)(DUMP_REGS + RG_STATE_REGS * 64) * 4;
+    static_assert(ST_END <= ROWS_CONT_WORDS, "rows_cont record");
+    SD void state_dump(u32* base, u32* rec, u32 d, u32 slot, u64 at) const {
+        const u32 nrows = (n_lb + 7) >> 3;
+        for (u32 rr = 0; rr < nrows; rr++) put_row(base + (u64)rr * NF * 64, rows.ldrow(rr));
+        put_regs(base + DUMP_REGS);
+        V h = scalars();
+        h = simd::sel(L() == 0u, d, h);
+        h = simd::sel(L() == 1u, slot, h);
+        h = simd::sel(L() == 2u, (u32)at, h);
+        h = simd::sel(L() == 3u, (u32)(at >> 32), h);
+        simd::st(rec, L(), h, L() < (u32)ST_END);
+    }
+    // ... into a fresh engine (every row zero); rec: the record, word i in lane i
+    SD void state_restore(const u32* base, V rec) {
+        set_scalars(rec);
+        status = 0;
+        const u32 nrows = (n_lb + 7) >> 3;
+        for (u32 rr = 0; rr < nrows && rr < (u32)NR; rr++) rows.strow(rr, get_row(base + (u64)rr * NF * 64));
+        rows.drop_row();
+        get_regs(base + DUMP_REGS);
+    }
+
     // ---------------------------------------------------------------- checkpoints (incremental replay)
     // Client.applyMsg is incremental (client.ts:805-836): a reader interleaves getText with messages.
     // With Params::ck_out set, a document this engine finishes also leaves its whole replay state in
@@ -2298,45 +1929,24 @@ struct RegEngine {
     // Region (words): header [0, CK_HDR), rows (NF fields of 64 words each, row by row), LV / HK / HS
     // (8 registers each), the arena semispace's [0, arenaTop) units, the map records [0, mapNext).
     static constexpr u32 CK_MAGIC = 0x434B5031u, CK_HDR = CK_HDR_WORDS;
-    static_assert(RG_ROWS <= CK_MAX_ROWS, "checkpoint regions hold the whole row plan");
-    enum : u32 { CK_VALID, CK_AT_LO, CK_AT_HI, CK_FLAGS, CK_NLB, CK_HEIGHT, CK_HEAPSIZE, CK_HEAPTOP, CK_MINSEQ,
-                 CK_CURSEQ, CK_SEGNEXT, CK_ARENATOP, CK_ARENASEL, CK_MAPNEXT, CK_NOPS, CK_NMSGS, CK_NGC, CK_MAXLB,
-                 CK_MW, CK_N };
-    static constexpr u32 CK_NF = 8 + (PROPS ? 1u : 0u) + (WIDE ? 1u : 0u);
+    // header words: the ST_* scalars at their own indices, around them
+    enum : u32 { CK_VALID, CK_AT_LO, CK_AT_HI, CK_FLAGS, CK_MW = ST_END, CK_N };
+    static_assert(CK_FLAGS < ST_BASE && CK_N <= CK_HDR, "checkpoint header");
     // words a checkpoint of a document with these capacities can take (the host sizes regions by it)
     SD static u64 ck_words(u32 arena_cap, u32 map_cap, u32 map_words) { return ck_region_words(arena_cap, map_cap, map_words); }
     SD void ckpt_save(u64 at) {
         const DocCfg& c = p.docs[doc];
-        if (!p.ck_out || !c.ck_cap || status || !rows_whole()) return;
+        if (!p.ck_out || !c.ck_cap || status || !rows.rows_whole(n_lb)) return;
         fence_arena();
         u32* base = p.ck_out + c.ck_out_off;
         const u32 nrows = (n_lb + 7) >> 3;
-        const u64 rows_end = CK_HDR + (u64)nrows * CK_NF * 64, regs_end = rows_end + 24 * 64;
+        const u64 rows_end = CK_HDR + (u64)nrows * NF * 64, regs_end = rows_end + RG_STATE_REGS * 64;
         const u64 ar_end = regs_end + ((u64)arenaTop + 1) / 2;
         const u64 end = ar_end + (PROPS ? (u64)mapNext * mw : 0);
         if (end > c.ck_cap) return;  // (the region stays invalid: the next pass replays from op 0)
         const V Lv = L();
-        for (u32 rr = 0; rr < nrows; rr++) {
-            const Row w = ldrow(rr);
-            u32* o = base + CK_HDR + (u64)rr * CK_NF * 64;
-            simd::st(o, Lv, w.len, simd::mk_all());
-            simd::st(o + 64, Lv, w.seq, simd::mk_all());
-            simd::st(o + 128, Lv, w.rseq, simd::mk_all());
-            simd::st(o + 192, Lv, w.meta, simd::mk_all());
-            simd::st(o + 256, Lv, w.cap, simd::mk_all());
-            simd::st(o + 320, Lv, w.toff, simd::mk_all());
-            simd::st(o + 384, Lv, w.rm, simd::mk_all());
-            simd::st(o + 448, Lv, w.sid, simd::mk_all());
-            if constexpr (PROPS) simd::st(o + 512, Lv, w.props, simd::mk_all());
-            if constexpr (WIDE) simd::st(o + 64 * (CK_NF - 1), Lv, w.rm2, simd::mk_all());
-        }
-        u32* g = base + rows_end;
-#pragma unroll
-        for (u32 i = 0; i < 8; i++) {
-            simd::st(g + 64 * i, Lv, LV.get(i), simd::mk_all());
-            simd::st(g + 64 * (8 + i), Lv, HK.get(i), simd::mk_all());
-            simd::st(g + 64 * (16 + i), Lv, HS.get(i), simd::mk_all());
-        }
+        for (u32 rr = 0; rr < nrows; rr++) put_row(base + CK_HDR + (u64)rr * NF * 64, rows.ldrow(rr));
+        put_regs(base + rows_end);
         copy_text(0, ARENA_BIT, arenaTop, reinterpret_cast<u16*>(base + regs_end));
         if constexpr (PROPS)
             for (u64 q = 0; q < (u64)mapNext * mw; q += 64) {
@@ -2345,11 +1955,11 @@ struct RegEngine {
                 simd::st(base + ar_end, i, simd::ld(maps, i, m), m);
             }
         const u32 flags = (PROPS ? 1u : 0u) | (WIDE ? 2u : 0u);
-        const u32 hv[CK_N] = {0u, (u32)at, (u32)(at >> 32), flags, n_lb, height, heapSize, (u32)heapTop, (u32)minSeq,
-                              (u32)curSeq, segNext, arenaTop, arenaSel, PROPS ? mapNext : 1u, ops_n(), msgs_n(), n_gc,
-                              max_lb, PROPS ? mw : 0u};
-        V h = simd::splat(0);
-        for (u32 i = 1; i < CK_N; i++) h = simd::sel(Lv == i, hv[i], h);
+        V h = scalars();
+        h = simd::sel(Lv == (u32)CK_AT_LO, (u32)at, h);
+        h = simd::sel(Lv == (u32)CK_AT_HI, (u32)(at >> 32), h);
+        h = simd::sel(Lv == (u32)CK_FLAGS, flags, h);
+        h = simd::sel(Lv == (u32)CK_MW, PROPS ? mw : 0u, h);
         simd::st(base, Lv, h, Lv < (u32)CK_N);
         // the valid word last, after every other word of the region is out
         simd::wave_fence();
@@ -2366,58 +1976,27 @@ struct RegEngine {
         const V h = simd::ld(base, Lv, Lv < (u32)CK_N);
         auto hw = [&](u32 i) MTE_LI { return simd::readlane(h, i); };
         const u64 at = (u64)hw(CK_AT_LO) | ((u64)hw(CK_AT_HI) << 32);
-        const u32 flags = hw(CK_FLAGS), nlb = hw(CK_NLB);
+        const u32 flags = hw(CK_FLAGS), nlb = hw(ST_NLB);
         const bool cprops = flags & 1u, cwide = (flags & 2u) != 0;
         // (a lean checkpoint continues on a PROPS / WIDE engine -- no maps, no high removers -- not the
         // other way round; a map table narrower than the records written is refused too)
         if (hw(CK_VALID) != CK_MAGIC || at != c.ck_at || (cprops && !PROPS) || (cwide && !WIDE) || nlb == 0 ||
-            nlb > NBLK || hw(CK_HEIGHT) > RG_LEVELS + 1 || hw(CK_ARENATOP) > arena_cap || hw(CK_SEGNEXT) > seg_cap ||
-            (cprops && (hw(CK_MW) != mw || hw(CK_MAPNEXT) > map_cap)))
+            nlb > NBLK || hw(ST_HEIGHT) > RG_LEVELS + 1 || hw(ST_ARENATOP) > arena_cap || hw(ST_SEGNEXT) > seg_cap ||
+            (cprops && (hw(CK_MW) != mw || hw(ST_MAPNEXT) > map_cap)))
             return i0;
         const u32 nrows = (nlb + 7) >> 3;
         if constexpr (PAGED) {
-            if (!grow_rows(nrows)) {  // the pool is full now: k_rows restarts it or the host re-runs it
+            if (!rows.grow_rows(nrows)) {  // the pool is full now: k_rows restarts it or the host re-runs it
                 status = REG_HANDOFF;
                 return i0;
             }
         }
-        const u32 cnf = 8 + (cprops ? 1u : 0u) + (cwide ? 1u : 0u);
-        for (u32 rr = 0; rr < nrows; rr++) {
-            const u32* o = base + CK_HDR + (u64)rr * cnf * 64;
-            Row w;
-            w.len = simd::ld(o, Lv, simd::mk_all());
-            w.seq = simd::ld(o + 64, Lv, simd::mk_all());
-            w.rseq = simd::ld(o + 128, Lv, simd::mk_all());
-            w.meta = simd::ld(o + 192, Lv, simd::mk_all());
-            w.cap = simd::ld(o + 256, Lv, simd::mk_all());
-            w.toff = simd::ld(o + 320, Lv, simd::mk_all());
-            w.rm = simd::ld(o + 384, Lv, simd::mk_all());
-            w.sid = simd::ld(o + 448, Lv, simd::mk_all());
-            if constexpr (PROPS) w.props = cprops ? simd::ld(o + 512, Lv, simd::mk_all()) : simd::splat(0);
-            if constexpr (WIDE) w.rm2 = cwide ? simd::ld(o + 64 * (cnf - 1), Lv, simd::mk_all()) : simd::splat(0);
-            strow(rr, w);
-        }
-        cr = NONE;
-        const u64 rows_end = CK_HDR + (u64)nrows * cnf * 64, regs_end = rows_end + 24 * 64;
-        const u32* g = base + rows_end;
-#pragma unroll
-        for (u32 i = 0; i < 8; i++) {
-            LV.set(i, simd::ld(g + 64 * i, Lv, simd::mk_all()));
-            HK.set(i, simd::ld(g + 64 * (8 + i), Lv, simd::mk_all()));
-            HS.set(i, simd::ld(g + 64 * (16 + i), Lv, simd::mk_all()));
-        }
-        n_lb = nlb;
-        height = hw(CK_HEIGHT);
-        heapSize = hw(CK_HEAPSIZE);
-        heapTop = (i32)hw(CK_HEAPTOP);
-        minSeq = (i32)hw(CK_MINSEQ);
-        curSeq = (i32)hw(CK_CURSEQ);
-        segNext = hw(CK_SEGNEXT);
-        arenaTop = hw(CK_ARENATOP);
-        arenaSel = hw(CK_ARENASEL) & 1u;
-        set_counts(hw(CK_NOPS), hw(CK_NMSGS));
-        n_gc = hw(CK_NGC);
-        max_lb = hw(CK_MAXLB);
+        const u32 cnf = Row::nf(cprops, cwide);
+        for (u32 rr = 0; rr < nrows; rr++) rows.strow(rr, get_row(base + CK_HDR + (u64)rr * cnf * 64, cprops, cwide));
+        rows.drop_row();
+        const u64 rows_end = CK_HDR + (u64)nrows * cnf * 64, regs_end = rows_end + RG_STATE_REGS * 64;
+        get_regs(base + rows_end);
+        set_scalars(h);
         // the arena text into this pass's semispace arenaSel (offsets kept: the rows' toff stay valid)
         {
             const u16* src = reinterpret_cast<const u16*>(base + regs_end);
@@ -2429,7 +2008,7 @@ struct RegEngine {
             }
         }
         if constexpr (PROPS) {
-            mapNext = cprops ? hw(CK_MAPNEXT) : 1u;
+            if (!cprops) mapNext = 1u;
             const u32* src = base + regs_end + ((u64)arenaTop + 1) / 2;
             const u32 nw = cprops ? mapNext * mw : 0u;
             for (u32 q = 0; q < nw; q += 64) {
@@ -2440,13 +2019,8 @@ struct RegEngine {
         }
         adirty = true;  // arena and map words written lane-parallel: fence before they are read
         if (simd::lane0()) {  // counters[12] / [13]: documents and op records resumed this pass
-#ifdef MTE_CPU
-            p.counters[12] += 1;
-            p.counters[13] += (u32)at;
-#else
-            atomicAdd(&p.counters[12], 1u);
-            atomicAdd(&p.counters[13], (u32)at);
-#endif
+            simd::count_add(&p.counters[12], 1u);
+            simd::count_add(&p.counters[13], (u32)at);
         }
         return i0 + at;
     }

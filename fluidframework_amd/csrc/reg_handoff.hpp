@@ -39,7 +39,7 @@ MTE_DEV bool reg_handoff(R& r, E& e) {
             left--;
         }
         const u32 rr = k >> 3, gb = (k & 7) * 8;
-        const auto w = r.ldrow(rr);
+        const auto w = r.rows.ldrow(rr);
         u32 olen = 0, cnt = 0;
         i32 mx = 0;
         for (u32 s = 0; s < 8; s++) {
@@ -94,7 +94,7 @@ MTE_DEV bool reg_handoff(R& r, E& e) {
     // encoding of live segments and needsScour differ
     lds_order();
     for (u32 rr = 0; rr < nrows; rr++) {
-        const auto w = r.ldrow(rr);
+        const auto w = r.rows.ldrow(rr);
         const uint4 v = make_uint4(w.len.x, w.seq.x, w.rseq.x, w.meta.x), a = make_uint4(w.cap.x, w.toff.x, w.rm.x, w.sid.x);
         const bool live = v.z == RSEQ_LIVE, ov = (v.w & F_OVL) != 0;
         const u32 m2 = (live ? (v.w & ~0xFF00u) : v.w) & ~NS_MASK;

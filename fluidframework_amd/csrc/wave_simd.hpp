@@ -188,6 +188,26 @@ SD void wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
 }
+// lanes below each lane set in m (mbcnt)
+SD V rank_below(u64 m) { return V{__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u))}; }
+// The wave reserves n of a shared counter (one atomic, by one lane): the counter's value before.
+SD u32 reserve(u32* ctr, u32 n) {
+    u32 o = 0;
+    if (lane0()) o = atomicAdd(ctr, n);
+    return __builtin_amdgcn_readfirstlane(o);
+}
+SD u64 reserve(u64* ctr, u64 n) {
+    u64 o = 0;
+    if (lane0()) o = atomicAdd((unsigned long long*)ctr, (unsigned long long)n);
+    const u32 lo = __builtin_amdgcn_readfirstlane((u32)o), hi = __builtin_amdgcn_readfirstlane((u32)(o >> 32));
+    return ((u64)hi << 32) | lo;
+}
+// n more of an event counter other waves count too; the caller is one lane (lane0())
+SD void count_add(u32* ctr, u32 n) { atomicAdd(ctr, n); }
+// Scheduling hints, nothing at run time. wait_loaded: v's load is waited for HERE, not at its first use.
+SD void wait_loaded(V v) { asm volatile("" ::"v"(v.x)); }
+// keep_branch: the conditional block this stands in stays a branch (is not turned into selects).
+SD void keep_branch() { asm volatile(""); }
 
 #else
 // ---------------------------------------------------------------------------------- CPU backend
@@ -372,6 +392,20 @@ SD void st(T* p, V idx, V v, B m) {
 SD void wave_fence() {}
 SD void lds_order() {}
 SD bool lane0() { return true; }  // the emulated wave performs a single store once
+SD V rank_below(u64 m) {
+    V r;
+    MTE_L r.x[l] = (u32)__builtin_popcountll(m & ((1ull << l) - 1ull));
+    return r;
+}
+template <class T>
+SD T reserve(T* ctr, T n) {
+    const T o = *ctr;
+    *ctr += n;
+    return o;
+}
+SD void count_add(u32* ctr, u32 n) { *ctr += n; }
+SD void wait_loaded(V) {}
+SD void keep_branch() {}
 #undef MTE_L
 #endif
 

@@ -33,7 +33,7 @@ static uint64_t replay_impl(const mte_op* ops, uint64_t n_ops, const uint16_t* p
                             uint32_t seg_cap, uint32_t arena_cap, uint32_t* out_vis, uint32_t* out_aux,
                             uint64_t* out_ovl, uint32_t out_cap, uint16_t* out_text, uint64_t out_text_cap,
                             DocRes* res, uint32_t pool_rows, const PropTables* pt = nullptr, uint64_t cut = 0,
-                            uint64_t* ck_resumed = nullptr) {
+                            uint64_t* ck_resumed = nullptr, bool via_dump = false) {
     std::vector<uint16_t> pay(payload, payload + payload_len + 1);
     std::vector<uint16_t> arena((size_t)arena_cap * 2 + 1, 0);
     DocCfg cfg;
@@ -93,7 +93,26 @@ static uint64_t replay_impl(const mte_op* ops, uint64_t n_ops, const uint16_t* p
     E* ep = make();
     uint64_t at0 = 0;
     std::vector<uint32_t> ck;
-    if (cut && cut < n_ops) {
+    if (via_dump && cut && cut < n_ops) {
+        // mid-pass continuation (k_rows' rows_dump -> k_rows_cont): ops [0, cut), the state dumped into
+        // a slot and a queue record, and a fresh engine restored from them goes on -- in the same pass,
+        // so the merge arena and the map table stay as they are
+        std::vector<uint32_t> slot(E::DUMP_BYTES / 4, 0), rec(64, 0);
+        const uint64_t a1 = ep->status ? 0 : ep->replay(0, cut);
+        if (ep->status || a1 != cut || !ep->rows.rows_whole(ep->n_lb)) {
+            // the first part did not reach the cut: nothing to continue (*ck_resumed stays 0)
+            memset(res, 0, sizeof *res);
+            res->status = ep->status ? ep->status : REG_HANDOFF;
+            delete ep;
+            return a1;
+        }
+        ep->state_dump(slot.data(), rec.data(), 0, 0, a1);
+        delete ep;
+        ep = make();
+        ep->state_restore(slot.data(), simd::ld(rec.data(), simd::lanes(), simd::mk_all()));
+        at0 = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
+        if (ck_resumed) *ck_resumed = at0;
+    } else if (cut && cut < n_ops) {
         // incremental replay (option retain): ops [0, cut) in a first "pass" that checkpoints, then a
         // fresh engine -- a fresh arena and map table -- continues from the checkpoint
         cfg.op_end = cut;
@@ -173,7 +192,8 @@ uint64_t regcpu_replay_props(const mte_op* ops, uint64_t n_ops, const uint16_t* 
 
 // Incremental replay: ops [0, cut) checkpointed (reg_engine.hpp ckpt_save), the rest continued on a
 // fresh engine from the checkpoint (ckpt_resume; *resumed = the op it went on from, 0 = it started
-// over). kind: 0 lean, 1 paged, 2 PROPS (3 PROPS paged, +4 WIDE) with the tables of regcpu_replay_props.
+// over). kind: 0 lean, 1 paged, 2 PROPS (3 PROPS paged, +4 WIDE) with the tables of regcpu_replay_props;
+// +16 (fixed-row kinds): the cut goes through k_rows' state dump instead (state_dump / state_restore).
 uint64_t regcpu_replay_split(const mte_op* ops, uint64_t n_ops, const uint16_t* payload, uint32_t payload_len,
                              uint32_t seg_cap, uint32_t arena_cap, uint32_t* out_vis, uint32_t* out_aux,
                              uint64_t* out_ovl, uint32_t out_cap, uint16_t* out_text, uint64_t out_text_cap,
@@ -182,22 +202,23 @@ uint64_t regcpu_replay_split(const mte_op* ops, uint64_t n_ops, const uint16_t* 
                              const uint32_t* prop_vals, const uint32_t* val_flags, uint32_t n_vals, uint32_t map_words,
                              uint32_t map_cap, uint32_t* out_maps) {
     PropTables t{(const mte_propset*)propsets, n_propsets, prop_keys, prop_vals, val_flags, n_vals, map_words, map_cap, out_maps};
-    switch (kind) {
+    const bool dump = (kind & 16u) != 0;
+    switch (kind & 15u) {
         case 0:
             return replay_impl<false, false>(ops, n_ops, payload, payload_len, seg_cap, arena_cap, out_vis, out_aux, out_ovl,
-                                             out_cap, out_text, out_text_cap, res, 0, nullptr, cut, resumed);
+                                             out_cap, out_text, out_text_cap, res, 0, nullptr, cut, resumed, dump);
         case 1:
             return replay_impl<true, false>(ops, n_ops, payload, payload_len, seg_cap, arena_cap, out_vis, out_aux, out_ovl,
                                             out_cap, out_text, out_text_cap, res, pool_rows, nullptr, cut, resumed);
         case 2:
             return replay_impl<false, true>(ops, n_ops, payload, payload_len, seg_cap, arena_cap, out_vis, out_aux, out_ovl,
-                                            out_cap, out_text, out_text_cap, res, 0, &t, cut, resumed);
+                                            out_cap, out_text, out_text_cap, res, 0, &t, cut, resumed, dump);
         case 3:
             return replay_impl<true, true>(ops, n_ops, payload, payload_len, seg_cap, arena_cap, out_vis, out_aux, out_ovl,
                                            out_cap, out_text, out_text_cap, res, pool_rows, &t, cut, resumed);
         case 6:
             return replay_impl<false, true, true>(ops, n_ops, payload, payload_len, seg_cap, arena_cap, out_vis, out_aux,
-                                                  out_ovl, out_cap, out_text, out_text_cap, res, 0, &t, cut, resumed);
+                                                  out_ovl, out_cap, out_text, out_text_cap, res, 0, &t, cut, resumed, dump);
         default:
             return replay_impl<true, true, true>(ops, n_ops, payload, payload_len, seg_cap, arena_cap, out_vis, out_aux,
                                                  out_ovl, out_cap, out_text, out_text_cap, res, pool_rows, &t, cut, resumed);

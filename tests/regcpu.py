@@ -145,7 +145,8 @@ def replay_props(ops, pay, gp, pool_rows=0, map_words=16, wide=False):
 def replay_split(ops, pay, cut, kind=0, pool_rows=16, gp=None, map_words=16, arena_cap=None):
     """Incremental replay on the CPU build (reg_engine.hpp ckpt_save / ckpt_resume): ops [0, cut) then a
     fresh engine continuing from the checkpoint. kind 0 lean, 1 paged, 2 PROPS, 3 PROPS paged, 6 / 7
-    PROPS + WIDE. Returns (stop index, op the continuation started from, DocRes, rows, text, maps)."""
+    PROPS + WIDE; + 16 on a fixed-row kind (0, 2, 6): the cut goes through k_rows' mid-pass state dump
+    (state_dump / state_restore, same arena and map table) instead of a checkpoint. Returns (stop index, op the continuation started from, DocRes, rows, text, maps)."""
     ops = np.ascontiguousarray(ops, dtype=_op_dtype())
     pay = np.ascontiguousarray(pay, dtype=np.uint16)
     n = len(ops)

@@ -3,7 +3,9 @@ engine: a log replayed in two passes -- ops [0, cut) checkpointed, then a fresh 
 merge arena and map table continuing from the checkpoint -- ends in exactly the state of the one-pass
 replay (Client.applyMsg is incremental, client.ts:805-836: the continued client is the same client).
 Every product instantiation (lean, paged, PROPS, PROPS paged, PROPS + WIDE), cuts anywhere a message
-ends, and the oracle as the anchor of the one-pass replay."""
+ends, and the oracle as the anchor of the one-pass replay. The fixed-row instantiations also take the
+cut through the other stored form of the state, k_rows' mid-pass dump (state_dump / state_restore: what
+rows_dump writes and k_rows_cont rebuilds on the device)."""
 import random
 
 import numpy as np
@@ -12,6 +14,7 @@ import pytest
 from tests import regcpu
 
 END_OF_MSG = 0x1
+VIA_DUMP = 16  # regcpu_replay_split: kind + 16 passes the cut through the rows-dump form
 
 
 def _cuts(ops, rng, k):
@@ -47,9 +50,15 @@ def _full(ops, pay, kind, pool, gp):
 
 @pytest.mark.parametrize("kind,gen,gid,n,clients", [(0, 2, 1, 6000, 8), (1, 2, 2, 6000, 8), (0, 5, 3, 4000, 3),
                                                     (2, 3, 4, 5000, 8), (3, 3, 5, 5000, 8), (6, 3, 6, 1200, 40),
-                                                    (7, 3, 2, 1100, 40), (2, 2, 8, 3000, 16)])
+                                                    (7, 3, 2, 1100, 40), (2, 2, 8, 3000, 16),
+                                                    # + VIA_DUMP: the cut goes through k_rows' mid-pass state
+                                                    # dump (state_dump / state_restore) instead of a checkpoint
+                                                    (0 + VIA_DUMP, 2, 1, 6000, 8), (0 + VIA_DUMP, 5, 3, 4000, 3),
+                                                    (2 + VIA_DUMP, 3, 4, 5000, 8), (6 + VIA_DUMP, 3, 6, 1200, 40),
+                                                    (2 + VIA_DUMP, 2, 8, 3000, 16)])
 def test_continued_replay_equals_one_pass(kind, gen, gid, n, clients):
     ops, pay = regcpu.generated(gen, gid, n, n_clients=clients, seed=1000)
+    split_kind, kind = kind, kind % VIA_DUMP
     gp = regcpu.GenProps() if kind >= 2 else None
     pool = 24 if kind in (1, 3) else 32
     full = _full(ops, pay, kind, pool, gp)
@@ -58,7 +67,7 @@ def test_continued_replay_equals_one_pass(kind, gen, gid, n, clients):
         regcpu.compare(ops, pay, pool_rows=pool if kind == 1 else None)
     rng = random.Random(gid)
     for cut in _cuts(ops, rng, 4) + [1]:
-        at, resumed, r, rows, text, maps = regcpu.replay_split(ops, pay, cut, kind=kind, pool_rows=pool, gp=gp)
+        at, resumed, r, rows, text, maps = regcpu.replay_split(ops, pay, cut, kind=split_kind, pool_rows=pool, gp=gp)
         assert resumed == cut, "the continuation started over instead of resuming"
         _same(full, (at, r, rows, text, maps if kind >= 2 else None))
 
