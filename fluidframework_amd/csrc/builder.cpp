@@ -1296,6 +1296,27 @@ int mte_builder_open_doc(mte_builder* b, const char* observer_name, uint32_t* do
     b->paths.emplace_back();
     return MTE_OK;
 }
+// ... whose log starts with a summary's records (Client.load before the first applyMsg)
+int mte_builder_open_doc_from_summary(mte_builder* b, const char* observer_name, const char* summary,
+                                      size_t summary_len, uint32_t* doc) {
+    if (!b || !summary || !doc) return MTE_E_ARG;
+    std::unique_ptr<DocBuild> db(new DocBuild(observer_name));
+    json::Value s;
+    try {
+        s = json::parse(summary, summary_len);
+    } catch (std::exception& ex) {
+        b->err = ex.what();
+        return MTE_E_PARSE;
+    }
+    if (int rc = add_summary(b, s, *db)) {
+        b->err = db->err;
+        return rc;
+    }
+    *doc = b->hb.n_docs() + (uint32_t)b->open.size();
+    b->open.push_back(std::move(db));
+    b->paths.emplace_back();
+    return MTE_OK;
+}
 int mte_builder_append_messages(mte_builder* b, uint32_t doc, const char* text, size_t len) {
     if (!b || !text) return MTE_E_ARG;
     const uint32_t nc = b->hb.n_docs();

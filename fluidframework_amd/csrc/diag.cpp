@@ -73,6 +73,8 @@ int mte_set_option(mte_engine* e, const char* key, int64_t value) {
         e->retain = value != 0;
         if (!e->retain) ck_forget(e);
     }
+    // block checkpoint regions of one checkpoint buffer (documents over it replay from op 0 every pass)
+    else if (k == "ck_blk_budget_mb") e->ck_blk_budget = (uint64_t)std::max<int64_t>(0, value) << 20;
     else return set_err(e, MTE_E_ARG, "unknown option " + k);
     return MTE_OK;
 }
@@ -114,6 +116,11 @@ int mte_get_info(mte_engine* e, const char* key, int64_t* value) {
     else if (k == "resumed_docs") *value = e->last_resumed_docs;  // option retain: documents continued ...
     else if (k == "resumed_ops") *value = e->last_resumed_ops;    // ... and the op records they skipped
     else if (k == "ck_offered") *value = e->last_ck_offered;      // documents whose log extends the last pass's
+    // ... the same for the documents the row engines cannot hold, continued by the block engine (k_blk_ck)
+    else if (k == "resumed_docs_blk") *value = e->last_resumed_docs_blk;
+    else if (k == "resumed_ops_blk") *value = (int64_t)e->last_resumed_ops_blk;
+    else if (k == "ck_blk_saved") *value = e->last_ck_blk_saved;      // block checkpoints written
+    else if (k == "ck_blk_skipped") *value = e->last_ck_blk_skipped;  // block documents over ck_blk_budget_mb
     else if (k == "out_text") {  // UTF-16 units Engine::finish gathered (counters[6..7])
         uint32_t ctr[8];
         if (int rc = read_counters(e, ctr, 8)) return rc;

@@ -2773,6 +2773,136 @@ struct Engine {
         wave_sync();
     }
 
+    // ---------------------------------------------------------------- checkpoints (incremental replay)
+    // The block engine's counterpart of the row engines' ckpt_save / ckpt_resume (reg_engine.hpp): with
+    // Params::ck_out set, a document this engine finishes leaves its whole replay state in its block
+    // checkpoint region (engine_types.hpp BlkCkLayout; DocCfg::ck_out_off, ck_cap words), and a later
+    // pass over a log that extends this one (the host checks the prefix, engine_run.cpp ck_match_batch)
+    // goes on from that state at op ck_at. Written against the array accessors, so one body serves
+    // every instantiation whose block ids are its own ([0, lbBump): the HBM and solo plans).
+    // A checkpoint written in one pass is read in a later one, across a kernel boundary.
+    template <class T>
+    MTE_DEV void ck_copy(T* __restrict__ dst, const T* __restrict__ src, u64 n) const {
+#pragma unroll 4
+        for (u64 i = L; i < n; i += 64) dst[i] = src[i];
+    }
+    // arena text: u16 units, two per access where source and destination are word-aligned
+    MTE_DEV void ck_copy_text(u16* dst, const u16* src, u32 n) const {
+        if ((((uintptr_t)dst | (uintptr_t)src) & 3u) == 0) {
+            ck_copy((u32*)dst, (const u32*)src, (u64)(n >> 1));
+            if ((n & 1u) && L == 0) dst[n - 1] = src[n - 1];
+        } else {
+            ck_copy(dst, src, (u64)n);
+        }
+    }
+    // at: op records of the document applied so far. Saves only a finished replay (status 0, every op
+    // applied) whose state fits the region; the magic word goes out last, after every other store of
+    // the wave is complete, so a torn region is never valid. Returns whether it saved.
+    MTE_DEV bool ckpt_save(u64 at) {
+        static_assert(sizeof(St) == BCK_ST_WORDS * 4, "St's scalars fill the header's BCK_ST words");
+        const DocCfg& c = p.docs[doc];
+        if (!p.ck_out || !c.ck_cap || st.status != 0 || at != c.op_end - c.op_begin) return false;
+        const bool o2 = ovl2 != nullptr;
+        // (the lean engine has no remover above 31: it never sets F_OVLHI, so no overlap word of its
+        // state is ever read, and none is saved)
+        const u32 nmap = FULL ? st.mapNext : 0u, nseg = FULL ? st.segNext : 0u;
+        const BlkCkLayout l = BlkCkLayout::of(st.lbBump, st.n_lb, st.inBump, st.heapSize, nseg, o2, st.arenaTop, nmap, mw);
+        if (l.words > c.ck_cap) return false;  // (the region stays invalid: the next pass replays from op 0)
+        wave_sync();  // arena text, overlap masks and map records other lanes wrote
+        st.adirty = st.gdirty = 0;
+        u32* base = p.ck_out + c.ck_out_off;
+        ck_copy((uint4*)(base + l.vis), (const uint4*)VIS(), (u64)st.lbBump * 8);
+        ck_copy((uint4*)(base + l.aux), (const uint4*)AUX(), (u64)st.lbBump * 8);
+        ck_copy(base + l.bmeta, (const u32*)BMETA(), (u64)st.lbBump);
+        ck_copy((uint4*)(base + l.ord), (const uint4*)ORD(), (u64)st.n_lb);
+        ck_copy(base + l.in_child, (const u32*)INCH(), (u64)st.inBump * 8);
+        ck_copy(base + l.in_cnt, (const u32*)INCNT(), (u64)st.inBump);
+        ck_copy(base + l.in_par, (const u32*)INPAR(), (u64)st.inBump);
+        ck_copy((uint2*)(base + l.heap), (const uint2*)(HEAP() + 1), (u64)st.heapSize);
+        ck_copy((u64*)(base + l.ovl), (const u64*)ovl, (u64)nseg);
+        if (o2) ck_copy((u64*)(base + l.ovl2), (const u64*)ovl2, (u64)nseg);
+        ck_copy_text((u16*)(base + l.arena), arena0 + (u64)st.arenaSel * arena_cap, st.arenaTop);
+        if (nmap) ck_copy((uint4*)(base + l.maps), (const uint4*)maps, (u64)nmap * mw / 4);
+        if (L >= BCK_STATS && L < BCK_STATS + ST_WORDS) base[L] = STATS()[L - BCK_STATS];
+        if (L == 0) {
+            u32 w[BCK_ST_WORDS];
+            __builtin_memcpy(w, &st, sizeof st);
+            for (u32 i = 0; i < BCK_ST_WORDS; i++) base[BCK_ST + i] = w[i];
+            base[BCK_AT_LO] = (u32)at;
+            base[BCK_AT_HI] = (u32)(at >> 32);
+            base[BCK_FLAGS] = (FULL ? 1u : 0u) | (o2 ? 2u : 0u);
+            base[BCK_MW] = mw;
+            base[BCK_CAP_BLK] = blk_cap();
+            base[BCK_CAP_ORD] = ord_cap();
+            base[BCK_CAP_IN] = in_cap();
+            base[BCK_CAP_HEAP] = heap_cap();
+            base[BCK_MAPS_LO] = (u32)l.maps;
+            base[BCK_MAPS_HI] = (u32)(l.maps >> 32);
+            base[BCK_NMAP] = nmap;
+        }
+        // the valid word last, after every other word of the region is out
+        wave_sync();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (L == 0) base[BCK_VALID] = BCK_MAGIC;
+        return true;
+    }
+    // Continue from the block checkpoint of the previous pass (DocCfg::ck_at op records in, region
+    // ck_in_off of Params::ck_in), after init(): validates the header, copies array by array into this
+    // engine's own arrays and restores St and the counters. Returns the op to go on from; on any
+    // mismatch the engine is left as it was and i0 comes back, so the document replays from op 0.
+    MTE_DEV u64 ckpt_resume(u64 i0) {
+        const DocCfg& c = p.docs[doc];
+        if (!p.ck_in || !c.ck_at || st.status) return i0;
+        const u32* base = p.ck_in + c.ck_in_off;
+        auto hw = [&](u32 i) { return U(base[i]); };
+        const u64 at = (u64)hw(BCK_AT_LO) | ((u64)hw(BCK_AT_HI) << 32);
+        const u32 flags = hw(BCK_FLAGS);
+        const bool cfull = flags & 1u, co2 = (flags & 2u) != 0;
+        St s;
+        {
+            u32 w[BCK_ST_WORDS];
+            for (u32 i = 0; i < BCK_ST_WORDS; i++) w[i] = hw(BCK_ST + i);
+            __builtin_memcpy(&s, w, sizeof s);
+        }
+        // (a lean checkpoint continues on a FULL engine -- no maps, no high removers -- not the other
+        // way round; a map table of another record width is refused, and so is every count beyond
+        // this engine's capacities)
+        if (hw(BCK_VALID) != BCK_MAGIC || at != c.ck_at || at > c.op_end - c.op_begin || (cfull && !FULL) ||
+            (co2 && !ovl2) || (cfull && hw(BCK_MW) != mw) || s.status != 0 || s.n_lb == 0 || s.n_lb > ord_cap() ||
+            s.lbBump > blk_cap() || s.inBump > in_cap() || s.heapSize > heap_cap() || s.segNext > seg_cap ||
+            s.arenaTop > arena_cap || s.arenaSel > 1u || (cfull && s.mapNext > map_cap))
+            return i0;
+        const u32 nmap = cfull ? s.mapNext : 0u, nseg = cfull ? s.segNext : 0u;
+        const BlkCkLayout l = BlkCkLayout::of(s.lbBump, s.n_lb, s.inBump, s.heapSize, nseg, co2, s.arenaTop, nmap, mw);
+        ck_copy((uint4*)VIS(), (const uint4*)(base + l.vis), (u64)s.lbBump * 8);
+        ck_copy((uint4*)AUX(), (const uint4*)(base + l.aux), (u64)s.lbBump * 8);
+        ck_copy((u32*)BMETA(), base + l.bmeta, (u64)s.lbBump);
+        ck_copy((uint4*)ORD(), (const uint4*)(base + l.ord), (u64)s.n_lb);
+        ck_copy((u32*)INCH(), base + l.in_child, (u64)s.inBump * 8);
+        ck_copy((u32*)INCNT(), base + l.in_cnt, (u64)s.inBump);
+        ck_copy((u32*)INPAR(), base + l.in_par, (u64)s.inBump);
+        ck_copy((uint2*)(HEAP() + 1), (const uint2*)(base + l.heap), (u64)s.heapSize);
+        ck_copy((u64*)ovl, (const u64*)(base + l.ovl), (u64)nseg);
+        if (co2) ck_copy((u64*)ovl2, (const u64*)(base + l.ovl2), (u64)nseg);
+        else if (ovl2)  // the window grew past 64 clients since: no segment has a remover above 63 yet
+            for (u64 i = L; i < s.segNext; i += 64) ovl2[i] = 0ull;
+        // the arena text into the same semispace of this pass's arena (offsets are semispace-relative)
+        ck_copy_text(arena0 + (u64)s.arenaSel * arena_cap, (const u16*)(base + l.arena), s.arenaTop);
+        if (nmap) ck_copy((uint4*)maps, (const uint4*)(base + l.maps), (u64)nmap * mw / 4);
+        if (L < ST_WORDS) STATS()[L] = base[BCK_STATS + L];
+        st = s;
+        st.credit = 0;
+        if (!cfull) st.mapNext = 1;
+        wave_sync();  // every array written lane-parallel: complete before the replay reads them
+        st.adirty = st.gdirty = 0;
+        if (L == 0) {  // counters[3] / [14..15]: documents and op records the block engine resumed
+            atomicAdd(&p.counters[3], 1u);
+            atomicAdd((unsigned long long*)&p.counters[14], (unsigned long long)at);
+        }
+        return i0 + at;
+    }
+
     // Synthetic workload generator: simulated writers draw valid ops from their own
     // view (getLength(refSeq, client)); each op is recorded into the doc's op/payload slots and
     // applied immediately, so the recorded log is exactly what a replay will see. The writers'

@@ -190,6 +190,9 @@ struct mte_engine {
     int ck_cur = -1;  // the buffer with the last pass's checkpoints (-1: none)
     struct CkDoc {
         uint64_t n_ops = 0, n_pay = 0, off = 0, h_ops = 0, h_pay = 0;
+        uint8_t kind = 0;  // the region's format: 0 a row checkpoint, 1 a block checkpoint (k_blk_ck)
+        uint8_t props = 0; // the log has an op with a property set (its map records hold key / value ids)
+        uint64_t cap = 0;  // words of the region
     };
     std::vector<CkDoc> ck_prev;        // per document of the last pass: what its checkpoint covers, and where
     std::vector<CkDoc> ck_load;        // per document of the loaded batch: its whole log's hashes
@@ -197,6 +200,20 @@ struct mte_engine {
     HostBatch ck_tabs;                 // the last pass's property tables (ids must keep their meaning)
     uint64_t ck_tabs_n = 0;            // their key / value / propset counts, 0 = none kept
     uint32_t ck_map_words = 0;
+    // block documents of a retained pass (engine level <= 1): the documents the row engines cannot
+    // replay (doc_not_rows) and those whose offered checkpoint is a block checkpoint run on k_blk_ck
+    // (mte_ckpt.hip), each in an HBM region and a worst-case map table of its own, and are taken out of
+    // the lists the other kernels consume for that pass
+    uint64_t ck_blk_budget = 1024ull << 20;  // option "ck_blk_budget_mb": block regions of one checkpoint buffer
+    std::vector<uint32_t> blk_list;          // this pass's block documents
+    std::vector<uint8_t> blk_ck;             // per document: 1 = on blk_list (writes a block checkpoint this pass),
+                                             // 2 = a block document over the budget (no checkpoint), 0 = neither
+    DevBuf<unsigned char> d_hbm_blk;         // their HBM regions (d_hbm is the re-run's, reallocated per pass)
+    DevBuf<uint32_t> d_maps_blk, d_blk_list, d_blk_saved;
+    std::vector<uint64_t> map_blk_off;       // UINT64_MAX = the document's maps are not in d_maps_blk
+    std::vector<uint32_t> map_blk_cap;
+    bool d_order_stale = false;              // d_order holds a pass's reduced list, not e->order
+    hipEvent_t ev_blk = nullptr;             // k_blk_ck done (second stream)
 
     // ---- last load and last run
     bool replayed = false;
@@ -217,6 +234,8 @@ struct mte_engine {
     double last_cell_pass_ms = 0;                       // a SharedMatrix batch's first (positions) pass
     double last_emit_ms = 0;
     uint32_t last_resumed_docs = 0, last_resumed_ops = 0, last_ck_offered = 0;  // option retain
+    uint32_t last_resumed_docs_blk = 0, last_ck_blk_saved = 0, last_ck_blk_skipped = 0;  // ... its block documents
+    uint64_t last_resumed_ops_blk = 0;
 
     // ---- downloaded final state
     bool downloaded = false;
@@ -273,7 +292,7 @@ uint32_t solo_count(const mte_engine* e);
 void wave_plan(const mte_engine* e, uint32_t nd, uint32_t& groups, uint32_t& hbm_waves, uint32_t* lds_active = nullptr,
                uint32_t n_solo = 0);
 void ck_forget(mte_engine* e);
-void ck_match_batch(mte_engine* e, const mte_batch* b);
+int ck_match_batch(mte_engine* e, const mte_batch* b);
 int run_kernel(mte_engine* e, bool gen);
 // Every device read of the read-back (readback.cpp makes no HIP call) and of the diagnostics: each is
 // one blocking hipMemcpy, except the two downloads, which copy once per replay.

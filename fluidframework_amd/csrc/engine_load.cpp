@@ -362,6 +362,7 @@ int mte_create(const mte_config* cfg, mte_engine** out) {
     HIP_TRY(e.get(), hipEventCreate(&e->ev_s1));
     HIP_TRY(e.get(), hipEventCreateWithFlags(&e->ev2, hipEventDisableTiming));
     HIP_TRY(e.get(), hipEventCreateWithFlags(&e->ev_gate, hipEventDisableTiming));
+    HIP_TRY(e.get(), hipEventCreateWithFlags(&e->ev_blk, hipEventDisableTiming));
     HIP_TRY(e.get(), hipEventCreate(&e->ev0));
     HIP_TRY(e.get(), hipEventCreate(&e->ev1));
     *out = e.release();
@@ -377,6 +378,7 @@ void mte_destroy(mte_engine* e) {
         if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]);
     }
     if (e->ev_gate) (void)hipEventDestroy(e->ev_gate);
+    if (e->ev_blk) (void)hipEventDestroy(e->ev_blk);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->ev2) (void)hipEventDestroy(e->ev2);
@@ -602,8 +604,8 @@ int mte_load(mte_engine* e, const mte_batch* b) {
     e->lean_ok = lean && !ext;
     e->ext_needed = ext;
     if ((rc = alloc_out_text(e))) return rc;
-    if (e->retain) ck_match_batch(e, b);
-    else ck_forget(e);
+    if (e->retain) return ck_match_batch(e, b);
+    ck_forget(e);
     return MTE_OK;
 }
 

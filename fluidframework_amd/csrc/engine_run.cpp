@@ -125,14 +125,49 @@ static uint64_t ck_hash_units(uint64_t h, const uint16_t* y, uint64_t n) {
 }
 // an op record as the engine reads it: MTE_F_CATCHUP marks the ops of the messages still above
 // minSeq at the END of a log (DocBuild::commit), which the row engines never read, so a prefix log
-// and its extension differ there and nowhere else
-static uint64_t ck_hash_ops(uint64_t h, const mte_op* o, uint64_t n) {
+// and its extension differ there and nowhere else.
+// A property-set id is hashed as the set's content (ps_hash: its keys' and values' interned texts in
+// order), not as the number a builder happened to give it: a fresh builder over longer logs of several
+// property-carrying documents numbers keys, values and sets in another order, and the log is the
+// same log. (Cell records' props is a value id of another table walk: hashed as it is.)
+static uint64_t ck_hash_ops(uint64_t h, const mte_op* o, uint64_t n, const std::vector<uint64_t>& ps_hash, bool* props = nullptr) {
     for (uint64_t i = 0; i < n; i++) {
         mte_op x = o[i];
         x.flags &= ~MTE_F_CATCHUP;
+        const bool set = x.props && x.props < ps_hash.size() && x.type != MTE_OP_CELL &&
+                         !(x.type == MTE_OP_NOOP && (x.flags & MTE_F_MX_MASK));
+        const uint64_t ph = set ? ps_hash[x.props] : 0;
+        if (set) {
+            x.props = 1;
+            if (props) *props = true;
+        }
         h = ck_hash(h, &x, sizeof x);
+        if (set) {
+            h = (h ^ ph) * 0x9E3779B97F4A7C15ull;
+            h ^= h >> 29;
+        }
     }
     return h;
+}
+// content hash of every property set of a batch's tables
+static std::vector<uint64_t> ck_ps_hashes(const HostBatch& t) {
+    std::vector<uint64_t> out(t.propsets.size(), 0);
+    for (size_t s = 0; s < t.propsets.size(); s++) {
+        uint64_t h = 0xCBF29CE484222325ull;
+        const mte_propset& ps = t.propsets[s];
+        for (uint32_t q = 0; q < ps.count && (size_t)ps.first + q < t.prop_keys.size(); q++) {
+            const uint32_t k = t.prop_keys[ps.first + q], v = t.prop_vals[ps.first + q];
+            auto mix = [&](const std::string& text, const std::vector<uint64_t>& off, uint32_t id, unsigned char sep) {
+                if ((size_t)id + 1 < off.size())
+                    for (uint64_t c = off[id]; c < off[id + 1]; c++) h = (h ^ (unsigned char)text[c]) * 0x100000001B3ull;
+                h = (h ^ sep) * 0x100000001B3ull;
+            };
+            mix(t.key_text, t.key_offsets, k, 0xFF);
+            mix(t.val_text, t.val_offsets, v, 0xFE);
+        }
+        out[s] = h ^ ((uint64_t)ps.count << 56);
+    }
+    return out;
 }
 static uint64_t ck_tabs_count(const HostBatch& t) {
     return (uint64_t)t.propsets.size() + t.prop_keys.size() + t.key_offsets.size() + t.val_offsets.size();
@@ -151,76 +186,8 @@ static bool ck_tabs_extend(const HostBatch& old, const HostBatch& nw) {
            pre(old.key_offsets, nw.key_offsets) && pre(old.key_text, nw.key_text) && pre(old.val_offsets, nw.val_offsets) &&
            pre(old.val_text, nw.val_text);
 }
-// mte_load with retain: which documents of the batch extend the last pass's (ck_match), and the
-// hashes of their whole logs for the next one
-void ck_match_batch(mte_engine* e, const mte_batch* b) {
-    const uint32_t nd = b->n_docs;
-    e->ck_match.assign(nd, 0);
-    e->ck_load.assign(nd, mte_engine::CkDoc{});
-    const bool same = e->ck_cur >= 0 && e->ck_prev.size() == nd && e->ck_tabs_n &&
-                      e->ck_map_words == e->map_words && ck_tabs_extend(e->ck_tabs, e->hb);
-    for (uint32_t d = 0; d < nd; d++) {
-        const mte_op* o = b->ops + b->doc_op_offsets[d];
-        const uint16_t* y = b->payload + b->doc_payload_offsets[d];
-        const uint64_t n = b->doc_op_offsets[d + 1] - b->doc_op_offsets[d];
-        const uint64_t np = b->doc_payload_offsets[d + 1] - b->doc_payload_offsets[d];
-        mte_engine::CkDoc& c = e->ck_load[d];
-        c.n_ops = n;
-        c.n_pay = np;
-        uint64_t ho = 0xCBF29CE484222325ull, hp = 0xCBF29CE484222325ull, k = 0, kp = 0;
-        if (same) {
-            const mte_engine::CkDoc& q = e->ck_prev[d];
-            if (q.n_ops && q.n_ops <= n && q.n_pay <= np) {
-                ho = ck_hash_ops(ho, o, q.n_ops);
-                hp = ck_hash_units(hp, y, q.n_pay);
-                k = q.n_ops;
-                kp = q.n_pay;
-                if (ho == q.h_ops && hp == q.h_pay) e->ck_match[d] = q.n_ops;
-            }
-        }
-        c.h_ops = ck_hash_ops(ho, o + k, n - k);
-        c.h_pay = ck_hash_units(hp, y + kp, np - kp);
-    }
-}
-// run_kernel with retain: this pass's regions, the previous pass's ones to continue from
-static int ck_begin(mte_engine* e) {
-    const uint32_t nd = (uint32_t)e->cfg.size();
-    const int out = e->ck_cur == 0 ? 1 : 0;
-    uint64_t tot = 0;
-    e->last_ck_offered = 0;
-    for (uint32_t d = 0; d < nd; d++) {
-        DocCfg& c = e->cfg[d];
-        c.ck_out_off = tot;
-        c.ck_cap = ck_region_words(c.arena_cap, c.map_cap, e->map_words);
-        tot += (c.ck_cap + 63) & ~63ull;
-        const bool have = e->ck_cur >= 0 && d < e->ck_match.size() && d < e->ck_prev.size() && e->ck_match[d];
-        c.ck_at = have ? e->ck_match[d] : 0;
-        c.ck_in_off = have ? e->ck_prev[d].off : 0;
-        e->last_ck_offered += have;
-    }
-    HIP_TRY(e, e->d_ck[out].fit(std::max<uint64_t>(tot, 64)));
-    HIP_TRY(e, hipMemsetAsync(e->d_ck[out].p, 0, tot * 4, e->stream));  // every region invalid until saved
-    HIP_TRY(e, hipMemcpyAsync(e->d_cfg.p, e->cfg.data(), nd * sizeof(DocCfg), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    e->P.ck_out = e->d_ck[out].p;
-    e->P.ck_in = e->ck_cur >= 0 ? e->d_ck[e->ck_cur].p : nullptr;
-    return MTE_OK;
-}
-// after the pass: its checkpoints are the ones the next pass continues from (the same batch replayed
-// again continues every document from its end)
-static void ck_end(mte_engine* e, const uint32_t* ctr) {
-    const uint32_t nd = (uint32_t)e->cfg.size();
-    e->ck_cur = e->ck_cur == 0 ? 1 : 0;
-    e->ck_prev.assign(nd, mte_engine::CkDoc{});
-    for (uint32_t d = 0; d < nd; d++) {
-        mte_engine::CkDoc& q = e->ck_prev[d];
-        if (d < e->ck_load.size()) q = e->ck_load[d];
-        q.off = e->cfg[d].ck_out_off;
-        q.n_ops = e->n_ops_doc[d];
-        q.n_pay = e->cfg[d].payload_len;
-    }
-    e->ck_match.assign(nd, 0);
-    for (uint32_t d = 0; d < nd; d++) e->ck_match[d] = e->ck_prev[d].n_ops;
+// the loaded batch's tables are the ones the kept checkpoints' ids mean
+static void ck_keep_tabs(mte_engine* e) {
     e->ck_tabs.propsets = e->hb.propsets;
     e->ck_tabs.prop_keys = e->hb.prop_keys;
     e->ck_tabs.prop_vals = e->hb.prop_vals;
@@ -230,10 +197,168 @@ static void ck_end(mte_engine* e, const uint32_t* ctr) {
     e->ck_tabs.val_text = e->hb.val_text;
     e->ck_tabs_n = 1 + ck_tabs_count(e->hb);
     e->ck_map_words = e->map_words;
+}
+// mte_load with retain: which documents of the batch extend the last pass's (ck_match), and the
+// hashes of their whole logs for the next one.
+// Tables that do not start with the last pass's (a fresh builder per pass over several
+// property-carrying documents interns in another order) still number the same keys and values: a
+// document without property sets has no id in its checkpoint and continues as it is; a block
+// checkpoint's map records are renumbered in place, once, to the loaded batch's ids (k_ck_xlate), and
+// the kept tables become the loaded ones. A row checkpoint with map records is not offered then.
+int ck_match_batch(mte_engine* e, const mte_batch* b) {
+    const uint32_t nd = b->n_docs;
+    e->ck_match.assign(nd, 0);
+    e->ck_load.assign(nd, mte_engine::CkDoc{});
+    const bool kept = e->ck_cur >= 0 && e->ck_prev.size() == nd && e->ck_tabs_n && e->ck_map_words == e->map_words;
+    const bool extend = kept && ck_tabs_extend(e->ck_tabs, e->hb);
+    const std::vector<uint64_t> ps_hash = ck_ps_hashes(e->hb);
+    for (uint32_t d = 0; d < nd; d++) {
+        const mte_op* o = b->ops + b->doc_op_offsets[d];
+        const uint16_t* y = b->payload + b->doc_payload_offsets[d];
+        const uint64_t n = b->doc_op_offsets[d + 1] - b->doc_op_offsets[d];
+        const uint64_t np = b->doc_payload_offsets[d + 1] - b->doc_payload_offsets[d];
+        mte_engine::CkDoc& c = e->ck_load[d];
+        c.n_ops = n;
+        c.n_pay = np;
+        uint64_t ho = 0xCBF29CE484222325ull, hp = 0xCBF29CE484222325ull, k = 0, kp = 0;
+        bool has_props = false;
+        if (kept) {
+            const mte_engine::CkDoc& q = e->ck_prev[d];
+            if (q.n_ops && q.n_ops <= n && q.n_pay <= np) {
+                ho = ck_hash_ops(ho, o, q.n_ops, ps_hash, &has_props);
+                hp = ck_hash_units(hp, y, q.n_pay);
+                k = q.n_ops;
+                kp = q.n_pay;
+                if (ho == q.h_ops && hp == q.h_pay && (extend || !q.props || q.kind == 1)) e->ck_match[d] = q.n_ops;
+            }
+        }
+        c.h_ops = ck_hash_ops(ho, o + k, n - k, ps_hash, &has_props);
+        c.h_pay = ck_hash_units(hp, y + kp, np - kp);
+        c.props = has_props;
+    }
+    if (!kept || extend) return MTE_OK;
+    // renumber the offered block checkpoints that hold ids; every other kept checkpoint with ids is in
+    // the old numbering still and is dropped, since the kept tables become this batch's
+    const HostBatch& old = e->ck_tabs;
+    auto xlate = [](const std::string& ot, const std::vector<uint64_t>& oo, const std::string& nt, const std::vector<uint64_t>& no) {
+        std::unordered_map<std::string, uint32_t> ids;
+        for (size_t i = 0; i + 1 < no.size(); i++) ids.emplace(nt.substr(no[i], no[i + 1] - no[i]), (uint32_t)i);
+        std::vector<uint32_t> x(oo.empty() ? 0 : oo.size() - 1, NONE);
+        for (size_t i = 0; i + 1 < oo.size(); i++) {
+            auto it = ids.find(ot.substr(oo[i], oo[i + 1] - oo[i]));
+            if (it != ids.end()) x[i] = it->second;
+        }
+        return x;
+    };
+    const std::vector<uint32_t> key_xl = xlate(old.key_text, old.key_offsets, e->hb.key_text, e->hb.key_offsets);
+    const std::vector<uint32_t> val_xl = xlate(old.val_text, old.val_offsets, e->hb.val_text, e->hb.val_offsets);
+    std::vector<uint64_t> off, cap;
+    for (uint32_t d = 0; d < nd; d++) {
+        mte_engine::CkDoc& q = e->ck_prev[d];
+        if (!q.props) continue;
+        if (e->ck_match[d] && q.kind == 1 && q.cap) {
+            off.push_back(q.off);
+            cap.push_back(q.cap);
+        } else {
+            e->ck_match[d] = 0;
+            q.n_ops = 0;  // (never offered again)
+        }
+    }
+    if (!off.empty()) {
+        DevBuf<uint64_t> d_off, d_cap;
+        DevBuf<uint32_t> d_kx, d_vx;
+        HIP_TRY(e, d_off.alloc(off.size()));
+        HIP_TRY(e, d_cap.alloc(cap.size()));
+        HIP_TRY(e, d_kx.alloc(key_xl.size()));
+        HIP_TRY(e, d_vx.alloc(val_xl.size()));
+        HIP_TRY(e, hipMemcpy(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_cap.p, cap.data(), cap.size() * 8, hipMemcpyHostToDevice));
+        if (!key_xl.empty()) HIP_TRY(e, hipMemcpy(d_kx.p, key_xl.data(), key_xl.size() * 4, hipMemcpyHostToDevice));
+        if (!val_xl.empty()) HIP_TRY(e, hipMemcpy(d_vx.p, val_xl.data(), val_xl.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(e, launch_ck_xlate(e->d_ck[e->ck_cur].p, d_off.p, d_cap.p, (uint32_t)off.size(), d_kx.p, (uint32_t)key_xl.size(),
+                                   d_vx.p, (uint32_t)val_xl.size(), e->map_words, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+    ck_keep_tabs(e);
+    return MTE_OK;
+}
+// the previous pass left document d a checkpoint (in a region of its own) that this pass's log extends
+static bool ck_have(const mte_engine* e, uint32_t d) {
+    return e->ck_cur >= 0 && d < e->ck_match.size() && d < e->ck_prev.size() && e->ck_match[d] && e->ck_prev[d].cap;
+}
+// run_kernel with retain: this pass's regions, the previous pass's ones to continue from.
+// The row regions first, then the block documents' (e->blk_ck: sized from the capacities of the engine
+// each runs on, cfg's hb_* and its worst-case map_cap). A checkpoint of the other kind than the
+// engine the document runs on this pass is not offered: the document replays from op 0.
+static int ck_begin(mte_engine* e) {
+    const uint32_t nd = (uint32_t)e->cfg.size();
+    const int out = e->ck_cur == 0 ? 1 : 0;
+    uint64_t tot = 0, row_tot = 0;
+    e->last_ck_offered = 0;
+    for (int blk = 0; blk < 2; blk++) {
+        for (uint32_t d = 0; d < nd; d++) {
+            DocCfg& c = e->cfg[d];
+            const bool is_blk = d < e->blk_ck.size() && e->blk_ck[d] == 1;
+            if (is_blk != (blk == 1)) continue;
+            c.ck_out_off = tot;
+            c.ck_cap = is_blk ? blk_ck_region_words(c.hb_blk, c.hb_ord, c.hb_in, c.hb_heap, c.seg_cap, c.ovl2_off != OVL2_NONE,
+                                                    c.arena_cap, c.map_cap, e->map_words)
+                              : ck_region_words(c.arena_cap, c.map_cap, e->map_words);
+            if (d < e->blk_ck.size() && e->blk_ck[d] == 2) c.ck_cap = 0;  // a block document over the budget
+            tot += (c.ck_cap + 63) & ~63ull;
+            const bool have = ck_have(e, d);
+            const bool use = have && (e->ck_prev[d].kind == 1) == is_blk;
+            c.ck_at = use ? e->ck_match[d] : 0;
+            c.ck_in_off = use ? e->ck_prev[d].off : 0;
+            e->last_ck_offered += have;
+        }
+        if (!blk) row_tot = tot;
+    }
+    HIP_TRY(e, e->d_ck[out].fit(std::max<uint64_t>(tot, 64)));
+    // every row region invalid until saved; k_blk_ck_clear clears the block regions' header words
+    HIP_TRY(e, hipMemsetAsync(e->d_ck[out].p, 0, row_tot * 4, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_cfg.p, e->cfg.data(), nd * sizeof(DocCfg), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    e->P.ck_out = e->d_ck[out].p;
+    e->P.ck_in = e->ck_cur >= 0 ? e->d_ck[e->ck_cur].p : nullptr;
+    return MTE_OK;
+}
+// after the pass: its checkpoints are the ones the next pass continues from (the same batch replayed
+// again continues every document from its end)
+static int ck_end(mte_engine* e, const uint32_t* ctr) {
+    const uint32_t nd = (uint32_t)e->cfg.size();
+    e->ck_cur = e->ck_cur == 0 ? 1 : 0;
+    e->ck_prev.assign(nd, mte_engine::CkDoc{});
+    for (uint32_t d = 0; d < nd; d++) {
+        mte_engine::CkDoc& q = e->ck_prev[d];
+        if (d < e->ck_load.size()) q = e->ck_load[d];
+        q.off = e->cfg[d].ck_out_off;
+        q.n_ops = e->n_ops_doc[d];
+        q.n_pay = e->cfg[d].payload_len;
+        // a block checkpoint: k_blk_ck's, or that of a document that left its rows mid-pass and finished in
+        // the checkpointing k_rows_cont (DocRes mode 6; it stays a block document from the next pass on)
+        q.kind = d < e->blk_ck.size() && e->blk_ck[d] == 1;
+        q.cap = e->cfg[d].ck_cap;
+        if (!q.cap) q.n_ops = 0;  // no region (over the block budget): nothing to offer
+        if (!q.kind && q.cap && d < e->res.size() && e->res[d].mode == 6 && e->res[d].status == 0) {
+            // (its region is a row region: the state fitted if the valid word is there; else nothing was
+            // saved and the document stays a row document)
+            uint32_t magic = 0;
+            HIP_TRY(e, hipMemcpy(&magic, e->P.ck_out + q.off, sizeof magic, hipMemcpyDeviceToHost));
+            q.kind = magic == BCK_MAGIC;
+            e->last_ck_blk_saved += q.kind;
+        }
+    }
+    e->ck_match.assign(nd, 0);
+    for (uint32_t d = 0; d < nd; d++) e->ck_match[d] = e->ck_prev[d].n_ops;
+    ck_keep_tabs(e);
     e->last_resumed_docs = ctr[12];
     e->last_resumed_ops = ctr[13];
+    e->last_resumed_docs_blk = ctr[3];
+    e->last_resumed_ops_blk = (uint64_t)ctr[14] | ((uint64_t)ctr[15] << 32);
     e->P.ck_out = nullptr;
     e->P.ck_in = nullptr;
+    return MTE_OK;
 }
 
 // HBM-resident capacities for a document that outgrew the LDS plan (blocks hold >= 4 segments
@@ -485,26 +610,25 @@ static int solo_timing(mte_engine* e, bool bulk) {
     return MTE_OK;
 }
 
-// second pass: the spilled documents, HBM-resident, one wave each, longest first
-static int rerun_spilled(mte_engine* e, bool gen, int full, const std::vector<uint32_t>& spill, float& hbm_ms) {
-    const uint32_t nd = (uint32_t)e->order.size(), nall = e->P.n_docs;
-    int rc;
-    uint64_t total = 0;
-    for (uint32_t d : spill) {
+// The listed documents in per-document HBM regions with worst-case capacities (DocCfg::hb_*, for
+// Engine::bind_hbm) and worst-case property-map tables of their own, for the host's re-run and for the
+// block documents of a retained pass. Sets e->cfg (the caller uploads it): hb_off from 0 in a buffer of
+// `total` bytes, map_off from 0 in a table of `mtot` records; keep_maps gets each document's load-time
+// (map_off, map_cap), which the caller puts back after the pass.
+static int layout_hbm_docs(mte_engine* e, bool gen, const std::vector<uint32_t>& list,
+                           std::vector<std::pair<uint64_t, uint32_t>>& keep_maps, uint64_t& total, uint64_t& mtot) {
+    total = mtot = 0;
+    keep_maps.clear();
+    for (uint32_t d : list) {
         uint64_t bytes;
         doc_hbm_caps(e->n_ops_doc[d], e->cfg[d], bytes);
         e->cfg[d].hb_off = total;
         total += (bytes + 255) & ~255ull;
     }
-    HIP_TRY(e, e->d_hbm.alloc(total));
-    // property maps: the load-time estimate (prop inserts + 4 per annotate) may be short for a
-    // re-run document; it gets the worst case, a new map per annotated character, in a table of
-    // its own (e->map_rr_off; the first pass's layout stays as it was)
-    std::vector<std::pair<uint64_t, uint32_t>> keep_maps;
-    uint64_t mtot = 0;
-    e->map_rr_off.assign(nall, UINT64_MAX);
-    e->map_rr_cap.assign(nall, 0);
-    for (uint32_t d : spill) {
+    // property maps: the load-time estimate (prop inserts + 4 per annotate) may be short for such a
+    // document; it gets the worst case, a new map per annotated character, in a table of its own
+    // (the first pass's layout stays as it was)
+    for (uint32_t d : list) {
         DocCfg& c = e->cfg[d];
         uint64_t cap = 16;
         if (gen) {
@@ -528,9 +652,25 @@ static int rerun_spilled(mte_engine* e, bool gen, int full, const std::vector<ui
         keep_maps.emplace_back(c.map_off, c.map_cap);
         c.map_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFF0ull);
         c.map_off = mtot;
-        e->map_rr_off[d] = mtot;
-        e->map_rr_cap[d] = c.map_cap;
         mtot += c.map_cap;
+    }
+    return MTE_OK;
+}
+
+// second pass: the spilled documents, HBM-resident, one wave each, longest first
+static int rerun_spilled(mte_engine* e, bool gen, int full, const std::vector<uint32_t>& spill, float& hbm_ms) {
+    const uint32_t nd = (uint32_t)e->order.size(), nall = e->P.n_docs;
+    int rc;
+    uint64_t total = 0, mtot = 0;
+    std::vector<std::pair<uint64_t, uint32_t>> keep_maps;
+    if ((rc = layout_hbm_docs(e, gen, spill, keep_maps, total, mtot))) return rc;
+    HIP_TRY(e, e->d_hbm.alloc(total));
+    // their maps are read back from the re-run table (e->map_rr_off)
+    e->map_rr_off.assign(nall, UINT64_MAX);
+    e->map_rr_cap.assign(nall, 0);
+    for (uint32_t d : spill) {
+        e->map_rr_off[d] = e->cfg[d].map_off;
+        e->map_rr_cap[d] = e->cfg[d].map_cap;
     }
     HIP_TRY(e, e->d_maps_rr.alloc(std::max<uint64_t>(mtot, 1) * e->map_words));
     if ((rc = upload(e, e->d_cfg, e->cfg))) return rc;
@@ -559,8 +699,103 @@ static int rerun_spilled(mte_engine* e, bool gen, int full, const std::vector<ui
     return MTE_OK;
 }
 
+// A retained pass's block documents (engine level <= 1): every document of the pass the row engines
+// cannot replay, and every one whose offered checkpoint is a block checkpoint (a k_rows document that
+// ever became a block document stays one). Lays out their HBM regions and map tables in e->cfg
+// (layout_hbm_docs; keep_maps as there) and admits them to the checkpoint budget shortest first: one
+// whose region does not fit is not listed (e->blk_ck 2) and runs where it runs without retain.
+static int blk_plan(mte_engine* e, std::vector<std::pair<uint64_t, uint32_t>>& keep_maps, uint64_t& total, uint64_t& mtot) {
+    const uint32_t nall = e->P.n_docs;
+    e->blk_list.clear();
+    e->blk_ck.assign(nall, 0);
+    total = mtot = 0;
+    std::vector<uint32_t> cand;
+    for (uint32_t d : e->order)
+        if ((e->doc_not_rows.size() == nall && e->doc_not_rows[d]) || (ck_have(e, d) && e->ck_prev[d].kind == 1)) cand.push_back(d);
+    if (cand.empty()) return MTE_OK;
+    int rc;
+    if ((rc = layout_hbm_docs(e, false, cand, keep_maps, total, mtot))) return rc;
+    std::vector<uint32_t> by_len(cand);
+    std::stable_sort(by_len.begin(), by_len.end(), [&](uint32_t a, uint32_t b) { return e->n_ops_doc[a] < e->n_ops_doc[b]; });
+    uint64_t used = 0;
+    for (uint32_t d : by_len) {
+        const DocCfg& c = e->cfg[d];
+        const uint64_t w = (blk_ck_region_words(c.hb_blk, c.hb_ord, c.hb_in, c.hb_heap, c.seg_cap, c.ovl2_off != OVL2_NONE,
+                                                c.arena_cap, c.map_cap, e->map_words) + 63) & ~63ull;
+        if ((used + w) * 4 <= e->ck_blk_budget) {
+            used += w;
+            e->blk_ck[d] = 1;
+        } else {
+            e->blk_ck[d] = 2;
+            e->last_ck_blk_skipped++;
+        }
+    }
+    for (uint32_t d : cand)
+        if (e->blk_ck[d] == 1) e->blk_list.push_back(d);
+    if (e->blk_list.size() != cand.size()) {  // lay out the admitted ones alone
+        for (size_t q = 0; q < cand.size(); q++) {
+            e->cfg[cand[q]].map_off = keep_maps[q].first;
+            e->cfg[cand[q]].map_cap = keep_maps[q].second;
+        }
+        if ((rc = layout_hbm_docs(e, false, e->blk_list, keep_maps, total, mtot))) return rc;
+    }
+    return MTE_OK;
+}
+
+namespace {
+// e->order for the length of a pass that runs without its block documents: put back when the pass
+// ends, however it ends (d_order is uploaded again by the next pass)
+struct BlkGuard {
+    mte_engine* e;
+    std::vector<uint32_t> all;
+    std::vector<std::pair<uint64_t, uint32_t>> keep;  // the block documents' load-time (map_off, map_cap)
+    bool on = false;
+    ~BlkGuard() {
+        if (!on) return;
+        e->order.swap(all);
+        for (size_t q = 0; q < e->blk_list.size() && q < keep.size(); q++) {
+            e->cfg[e->blk_list[q]].map_off = keep[q].first;
+            e->cfg[e->blk_list[q]].map_cap = keep[q].second;
+        }
+    }
+};
+}  // namespace
+
 int run_kernel(mte_engine* e, bool gen) {
     HIP_TRY(e, hipSetDevice(e->device));
+    int rc;
+    if (e->d_order_stale) {  // (the last pass ran on a reduced list and its block documents' map tables)
+        if ((rc = upload(e, e->d_order, e->order)) || (rc = upload(e, e->d_cfg, e->cfg))) return rc;
+        e->d_order_stale = false;
+    }
+    // option retain: checkpoints out, and in from the last pass (not for the generator, whose batch
+    // is made in the pass, nor the two passes of a SharedMatrix batch)
+    const bool ck = e->retain && !gen && e->P.cell_mode == 0;
+    // engine level (engine.hpp): the generator always runs FULL
+    if (!gen) {
+        e->ext_needed = e->ext_perm || (e->ext_cu && e->legacy);
+        e->lean_ok = e->lean_base && !e->ext_needed;
+    }
+    // a retained pass at level <= 1 runs its block documents on k_blk_ck; the rest of the pass is
+    // routed as if they were not in the batch
+    uint64_t blk_bytes = 0, blk_maps = 0;
+    e->blk_list.clear();
+    e->blk_ck.clear();
+    e->map_blk_off.clear();
+    e->last_ck_blk_skipped = 0;
+    BlkGuard og{e};
+    if (ck && !e->ext_needed) {
+        HIP_TRY(e, hipStreamSynchronize(e->stream));  // (layout_hbm_docs reads the uploaded op records)
+        if ((rc = blk_plan(e, og.keep, blk_bytes, blk_maps))) return rc;
+        if (!e->blk_list.empty()) {
+            og.all = e->order;
+            og.on = true;
+            e->order.erase(std::remove_if(e->order.begin(), e->order.end(), [&](uint32_t d) { return e->blk_ck[d] == 1; }),
+                           e->order.end());
+            e->d_order_stale = true;
+            if ((rc = upload(e, e->d_order, e->order))) return rc;
+        }
+    }
     // nd: the documents this pass replays (e->order, LPT; a SharedMatrix batch's first pass runs
     // only its cell documents), nall: the batch's documents (results are indexed by document)
     const uint32_t nd = (uint32_t)e->order.size(), nall = e->P.n_docs;
@@ -570,19 +805,10 @@ int run_kernel(mte_engine* e, bool gen) {
     e->P.reg_lb_limit = e->reg_lb_limit;
     e->P.doc_list = e->d_order.p;
     e->P.n_list = nd;
-    int rc;
     if ((rc = alloc_slots(e))) return rc;  // options may have changed the wave plan
-    // option retain: checkpoints out, and in from the last pass (not for the generator, whose batch
-    // is made in the pass, nor the two passes of a SharedMatrix batch)
-    const bool ck = e->retain && !gen && e->P.cell_mode == 0;
     e->P.ck_in = e->P.ck_out = nullptr;
     if (ck && (rc = ck_begin(e))) return rc;
     const uint32_t n_solo = e->P.n_solo;
-    // engine level (engine.hpp): the generator always runs FULL
-    if (!gen) {
-        e->ext_needed = e->ext_perm || (e->ext_cu && e->legacy);
-        e->lean_ok = e->lean_base && !e->ext_needed;
-    }
     const Route r = route(e, gen, ck);
     const int full = r.full;
     const uint32_t rows = r.rows, groups = r.groups, hbm_waves = r.hbm_waves;
@@ -602,6 +828,20 @@ int run_kernel(mte_engine* e, bool gen) {
     HIP_TRY(e, hipMemsetAsync(e->d_slot_bits.p, 0, e->d_slot_bits.n * sizeof(uint32_t), s_main));
     HIP_TRY(e, hipMemsetAsync(e->d_prof.p, 0, e->d_prof.n * sizeof(uint64_t), s_main));  // profiling build
     HIP_TRY(e, hipMemsetAsync(e->d_solo_started.p, 0, sizeof(uint32_t), s_main));  // k_solo_gate's counter
+    const uint32_t n_blk = (uint32_t)e->blk_list.size();
+    if (n_blk) {  // k_blk_ck's regions, map tables, list and counter
+        HIP_TRY(e, e->d_hbm_blk.fit(blk_bytes));
+        HIP_TRY(e, e->d_maps_blk.fit(std::max<uint64_t>(blk_maps, 1) * e->map_words));
+        HIP_TRY(e, e->d_blk_saved.fit(1));
+        e->map_blk_off.assign(nall, UINT64_MAX);
+        e->map_blk_cap.assign(nall, 0);
+        for (uint32_t d : e->blk_list) {
+            e->map_blk_off[d] = e->cfg[d].map_off;
+            e->map_blk_cap[d] = e->cfg[d].map_cap;
+        }
+        if ((rc = upload(e, e->d_blk_list, e->blk_list))) return rc;
+        HIP_TRY(e, hipMemsetAsync(e->d_blk_saved.p, 0, sizeof(uint32_t), s_main));
+    }
     HIP_TRY(e, hipEventRecord(e->ev0, s_main));
     std::vector<uint32_t> spill;
     e->map_rr_off.clear();  // (set again below for this pass's re-run documents)
@@ -626,7 +866,7 @@ int run_kernel(mte_engine* e, bool gen) {
         HIP_TRY(e, launch_rows(e->P, per, std::min<uint32_t>(cus, (nd - n_solo + per - 1) / per), full == 1,
                                full == 1 && e->rows_wide, ck, s_main));
         // documents k_rows handed to HBM slots between two ops continue here (k_rows_cont)
-        HIP_TRY(e, launch_rows_cont(e->P, full == 1, full == 1 && e->rows_wide, e->P.n_hslots, s_main));
+        HIP_TRY(e, launch_rows_cont(e->P, full == 1, full == 1 && e->rows_wide, ck, e->P.n_hslots, s_main));
     }
     // k_hbmq: one workgroup (wave) per document; those that find the queue drained exit at once
     if (hbm_waves && !groups) {
@@ -636,6 +876,21 @@ int run_kernel(mte_engine* e, bool gen) {
         HIP_TRY(e, launch_hbmq(e->P, gen, full, nd, s_hbmq));
         HIP_TRY(e, hipEventRecord(e->ev2, s_hbmq));
         HIP_TRY(e, hipStreamWaitEvent(s_main, e->ev2, 0));
+    }
+    // the block documents of a retained pass: k_blk_ck on the second stream beside the bulk, each in
+    // its own HBM region and map table (read back like the re-run documents', fetch_map_record),
+    // joined before emission
+    if (n_blk) {
+        HIP_TRY(e, hipStreamWaitEvent(s_hbmq, e->ev_gate, 0));  // (its list and counter went out before ev0)
+        Params pb = e->P;
+        pb.doc_list = e->d_blk_list.p;
+        pb.n_list = n_blk;
+        pb.hbm = e->d_hbm_blk.p;
+        pb.maps = e->d_maps_blk.p;
+        pb.map_rerun = 1;  // (worst-case tables: a full one is a capacity failure)
+        HIP_TRY(e, launch_blk_ck(pb, full, n_blk, e->d_blk_saved.p, s_hbmq));
+        HIP_TRY(e, hipEventRecord(e->ev_blk, s_hbmq));
+        HIP_TRY(e, hipStreamWaitEvent(s_main, e->ev_blk, 0));
     }
     const bool emit = !gen && e->emit_opt;
     e->emitted_legacy = e->legacy;
@@ -673,9 +928,10 @@ int run_kernel(mte_engine* e, bool gen) {
     e->last_hbm_ms = hbm_ms;
     e->last_kernel_ms = (double)lds_ms + hbm_ms;
     e->last_emit_ms = 0;
-    if (emit) {  // round 1: the solo documents and those the host re-ran
+    if (emit) {  // round 1: the solo documents, those the host re-ran and k_blk_ck's
         std::vector<uint32_t> rest(e->order.begin(), e->order.begin() + std::min<uint32_t>(n_solo, nd));
         rest.insert(rest.end(), spill.begin(), spill.end());
+        rest.insert(rest.end(), e->blk_list.begin(), e->blk_list.end());
         HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
         if ((erc = emit_list(e, 1, rest, e->stream))) return erc;
         HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
@@ -686,8 +942,12 @@ int run_kernel(mte_engine* e, bool gen) {
     }
     e->res.resize(nall);
     HIP_TRY(e, hipMemcpy(e->res.data(), e->d_res.p, nall * sizeof(DocRes), hipMemcpyDeviceToHost));
-    if (ck) ck_end(e, ctr);
-    else if (!gen) e->last_resumed_docs = e->last_resumed_ops = 0;
+    if (!gen) {
+        e->last_resumed_docs = e->last_resumed_ops = e->last_resumed_docs_blk = e->last_ck_blk_saved = 0;
+        e->last_resumed_ops_blk = 0;
+    }
+    if (n_blk) HIP_TRY(e, hipMemcpy(&e->last_ck_blk_saved, e->d_blk_saved.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ck && (rc = ck_end(e, ctr))) return rc;
     e->replayed = true;
     e->downloaded = false;
     return MTE_OK;
@@ -789,9 +1049,13 @@ int ensure_emit_download(mte_engine* e) {
 // the re-run table when the host re-ran the document (rerun_spilled), else in the load-time one.
 int fetch_map_record(mte_engine* e, uint32_t d, uint32_t id, uint32_t* w) {
     const bool rr = d < e->map_rr_off.size() && e->map_rr_off[d] != UINT64_MAX;
-    if (id >= (rr ? e->map_rr_cap[d] : e->cfg[d].map_cap))
+    // (a block document of a retained pass: k_blk_ck's table)
+    const bool bk = !rr && d < e->map_blk_off.size() && e->map_blk_off[d] != UINT64_MAX;
+    if (id >= (rr ? e->map_rr_cap[d] : bk ? e->map_blk_cap[d] : e->cfg[d].map_cap))
         return set_err(e, MTE_E_STATE, "catch-up: property map id out of range");
-    const uint32_t* base = rr ? e->d_maps_rr.p + e->map_rr_off[d] * e->map_words : e->d_maps.p + e->cfg[d].map_off * e->map_words;
+    const uint32_t* base = rr   ? e->d_maps_rr.p + e->map_rr_off[d] * e->map_words
+                           : bk ? e->d_maps_blk.p + e->map_blk_off[d] * e->map_words
+                                : e->d_maps.p + e->cfg[d].map_off * e->map_words;
     HIP_TRY(e, hipMemcpy(w, base + (uint64_t)id * e->map_words, e->map_words * 4, hipMemcpyDeviceToHost));
     return MTE_OK;
 }

@@ -152,7 +152,8 @@ struct DocCfg {
     u32 gid;           // global document id (summary records; the generator's per-document seed)
     // incremental replay (option retain, reg_engine.hpp ckpt_*): this pass's checkpoint region in
     // Params::ck_out (ck_cap words, 0 = none) and, when the loaded log extends the previous pass's, the
-    // previous region in Params::ck_in and the op records it covers (ck_at, 0 = replay from op 0)
+    // previous region in Params::ck_in and the op records it covers (ck_at, 0 = replay from op 0); a
+    // block document's regions (k_blk_ck, BlkCkLayout below) lie behind the row regions of the same buffers
     u64 ck_out_off, ck_cap, ck_in_off, ck_at;
 };
 
@@ -216,10 +217,13 @@ struct Params {
     u32* out_maps;            // property map of each final row with props (MAP_WORDS per row), or null
     u64 out_text_cap;
     u32* counters;            // [0] doc queue, [1] output rows, [2] docs re-run by the host,
-                              // [3] unused, [4] docs continued HBM-resident, [5] k_lds critical-path
+                              // [3] docs the block engine resumed from a checkpoint (k_blk_ck),
+                              // [4] docs continued HBM-resident, [5] k_lds critical-path
                               // queue, [6..7] output text units (u64),
                               // [8] / [9] k_rows restarts pushed / popped, [10] k_rows documents
-                              // dumped for k_rows_cont (16 words, zeroed before each pass)
+                              // dumped for k_rows_cont, [12] / [13] docs / op records the row
+                              // engines resumed, [14..15] op records the block engine skipped (u64)
+                              // (16 words, zeroed before each pass)
     unsigned char* spill;     // per-wave HBM slots (slot_bytes each): LDS waves 0..8G-1 keep theirs for
                               // documents that outgrow the LDS plan, HBM waves use slot_hbm0 + blockIdx
     u64 slot_bytes;
@@ -279,6 +283,72 @@ constexpr u32 RG_STATE_REGS = 24;   // interior levels, heap keys, heap segment 
 MTE_HOSTDEV_ u64 ck_region_words(u32 arena_cap, u32 map_cap, u32 map_words) {
     return CK_HDR_WORDS + (u64)CK_MAX_ROWS * ROW_FIELDS_MAX * 64 + RG_STATE_REGS * 64 + ((u64)arena_cap + 1) / 2 +
            (u64)map_cap * map_words;
+}
+
+// A block checkpoint region (option retain, engine.hpp Engine::ckpt_save): the stored state of a
+// document the block engine (Engine<LDSM, SOLO, LVL>: leaf blocks, interior nodes, heap) finished, in
+// the same role as ck_region_words for the row engines. Word offsets from the region's start; the
+// header, then every state array at a 16-byte boundary. The counts are the ones in use at the save
+// (Engine::ckpt_save) or the capacities of the engine the document runs on (the host's sizing):
+//   vis / aux   blk * 8 slots of 16 B        (block ids [0, lbBump))
+//   bmeta       blk words
+//   ord         ord entries of 16 B          ([0, n_lb))
+//   in_child    in * 8 words, in_cnt / in_par: in words each   ([0, inBump))
+//   heap        heap entries of 8 B          (heap[1 .. heapSize])
+//   ovl (ovl2)  seg u64 each                 ([0, segNext), FULL engines only: the lean one never reads
+//                                            them; ovl2 only for windows above 64 clients)
+//   arena       arena u16 units              (the live semispace's [0, arenaTop))
+//   maps        map_recs * map_words words   ([0, mapNext))
+// Header words (BCK_*): magic, op records covered (64-bit), flags (bit 0: written by a FULL engine,
+// bit 1: ovl2 saved), map_words, the source capacities, every scalar of St (BCK_ST_WORDS words at
+// BCK_ST), the ST_WORDS per-document counters at BCK_STATS. The hint table is not saved (hints are
+// verified on use).
+constexpr u32 BCK_MAGIC = 0x434B4231u, BCK_HDR_WORDS = 64;
+constexpr u32 BCK_VALID = 0, BCK_AT_LO = 1, BCK_AT_HI = 2, BCK_FLAGS = 3, BCK_MW = 4, BCK_CAP_BLK = 5, BCK_CAP_ORD = 6,
+              BCK_CAP_IN = 7, BCK_CAP_HEAP = 8, BCK_ST = 9, BCK_ST_WORDS = 20, BCK_STATS = 32,
+              // where the map records lie and how many (k_ck_xlate renumbers their key / value ids in
+              // place when a later batch's interned tables number the same keys and values differently)
+              BCK_MAPS_LO = 29, BCK_MAPS_HI = 30, BCK_NMAP = 31;
+static_assert(BCK_ST + BCK_ST_WORDS <= BCK_STATS && BCK_STATS + ST_WORDS <= BCK_HDR_WORDS, "block checkpoint header");
+struct BlkCkLayout {
+    MTE_HOSTDEV_ static u64 a4(u64 words) { return (words + 3) & ~3ull; }
+    u64 vis, aux, bmeta, ord, in_child, in_cnt, in_par, heap, ovl, ovl2, arena, maps, words;
+    MTE_HOSTDEV_ static BlkCkLayout of(u32 blk, u32 ord, u32 in, u32 heap, u32 seg, bool has_ovl2, u32 arena_units,
+                                       u32 map_recs, u32 map_words) {
+        BlkCkLayout l;
+        u64 o = BCK_HDR_WORDS;
+        l.vis = o;
+        o += (u64)blk * 8 * 4;
+        l.aux = o;
+        o += (u64)blk * 8 * 4;
+        l.bmeta = o;
+        o += a4(blk);
+        l.ord = o;
+        o += (u64)ord * 4;
+        l.in_child = o;
+        o += a4((u64)in * 8);
+        l.in_cnt = o;
+        o += a4(in);
+        l.in_par = o;
+        o += a4(in);
+        l.heap = o;
+        o += a4((u64)heap * 2);
+        l.ovl = o;
+        o += a4((u64)seg * 2);
+        l.ovl2 = o;
+        o += has_ovl2 ? a4((u64)seg * 2) : 0;
+        l.arena = o;
+        o += a4(((u64)arena_units + 1) / 2);
+        l.maps = o;
+        o += a4((u64)map_recs * map_words);
+        l.words = o;
+        return l;
+    }
+};
+// words of one document's block checkpoint region, from the capacities of the engine it runs on
+MTE_HOSTDEV_ u64 blk_ck_region_words(u32 blk, u32 ord, u32 in, u32 heap, u32 seg_cap, bool has_ovl2, u32 arena_cap,
+                                     u32 map_cap, u32 map_words) {
+    return BlkCkLayout::of(blk, ord, in, heap, seg_cap, has_ovl2, arena_cap, map_cap, map_words).words;
 }
 
 constexpr u32 SOLO_CLK_SLOTS = 64;  // solo workgroups with clock stamps (Params::solo_clk)

@@ -231,7 +231,10 @@ MTE_DEV u32 rows_dump(const Params& p, R& r, u32 d, u64 at) {
 // in its LDS (the rows at the k_solo layout's offsets, 32 rows), hands it to the HBM engine in the same
 // slot, replays the rest of its ops (DocRes mode 6) and gives the slot back. One workgroup per slot
 // (every record holds one); those past the queue exit at once.
-template <bool PROPS, bool WIDE>
+// CK (option retain): a document that finishes here also leaves a block checkpoint (Engine::ckpt_save)
+// in its checkpoint region, where it fits, so the next pass continues it on k_blk_ck -- a separate
+// instantiation, as k_rows<.., CK>.
+template <bool PROPS, bool WIDE, bool CK = false>
 __global__ __launch_bounds__(64) void k_rows_cont(Params p) {
     typedef RegEngine<(int)RG_ROWS, false, PROPS, WIDE> R;
     constexpr int LVL = PROPS ? 1 : 0;
@@ -256,28 +259,37 @@ __global__ __launch_bounds__(64) void k_rows_cont(Params p) {
             if (L == 0) p.res[d].spill_why |= 2u;
         } else {
             h.from_rows = true;
-            h.replay_run(at);
-            if (h.st.status == DOC_SPILL) h.mark_spilled();
-            else h.finish();
+            const u64 end = h.replay_run(at);
+            if (h.st.status == DOC_SPILL) {
+                h.mark_spilled();
+            } else {
+                if constexpr (CK) h.ckpt_save(end - p.docs[d].op_begin);
+                h.finish();
+            }
         }
     }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     if (L == 0) atomicAnd(&p.slot_bits[slot >> 5], ~(1u << (slot & 31)));
 }
-template <bool PROPS, bool WIDE>
+template <bool PROPS, bool WIDE, bool CK>
 static hipError_t launch_rows_cont_t(const Params& p, u32 n_slots, hipStream_t s) {
-    const void* k = (const void*)k_rows_cont<PROPS, WIDE>;
+    const void* k = (const void*)k_rows_cont<PROPS, WIDE, CK>;
     constexpr u32 LDS = RowsGeom<PROPS, WIDE>::CONT_LDS;
     static const hipError_t attr = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     if (attr != hipSuccess) return attr;
     void* args[] = {(void*)&p};
     return hipLaunchKernel(k, dim3(n_slots), dim3(64), args, LDS, s);
 }
-hipError_t launch_rows_cont(const Params& p, bool props, bool wide, u32 n_slots, hipStream_t s) {
+hipError_t launch_rows_cont(const Params& p, bool props, bool wide, bool ck, u32 n_slots, hipStream_t s) {
     if (!n_slots || !p.rows_cont) return hipSuccess;
-    if (wide) return props ? launch_rows_cont_t<true, true>(p, n_slots, s) : hipErrorInvalidValue;
-    return props ? launch_rows_cont_t<true, false>(p, n_slots, s) : launch_rows_cont_t<false, false>(p, n_slots, s);
+    if (wide && !props) return hipErrorInvalidValue;
+    if (ck) {
+        if (wide) return launch_rows_cont_t<true, true, true>(p, n_slots, s);
+        return props ? launch_rows_cont_t<true, false, true>(p, n_slots, s) : launch_rows_cont_t<false, false, true>(p, n_slots, s);
+    }
+    if (wide) return launch_rows_cont_t<true, true, false>(p, n_slots, s);
+    return props ? launch_rows_cont_t<true, false, false>(p, n_slots, s) : launch_rows_cont_t<false, false, false>(p, n_slots, s);
 }
 
 // CK (option retain, 4 waves only): documents continue from the previous pass's checkpoints and leave

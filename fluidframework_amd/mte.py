@@ -105,6 +105,7 @@ EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mt
            "mte_rccl_comm_create", "mte_rccl_comm_destroy", "mte_gather_summaries", "mte_gather_summaries_alloc", "mte_free", "mte_builder_create", "mte_builder_add_doc", "mte_builder_add_doc_from_summary", "mte_builder_add_container_log", "mte_builder_doc_path",
            "mte_builder_add_matrix_log", "mte_builder_add_matrix_from_summary", "mte_snapshot_matrix",
            "mte_builder_batch", "mte_builder_open_doc", "mte_builder_append_messages", "mte_retain",
+           "mte_builder_open_doc_from_summary",
            "mte_builder_error", "mte_builder_destroy"]
 
 _lib = None
@@ -169,6 +170,9 @@ def lib():
             L.mte_builder_open_doc.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)]
             L.mte_builder_append_messages.argtypes = [vp, ctypes.c_uint32, ctypes.c_char_p, sz]
             L.mte_retain.argtypes = [vp, ctypes.c_int]
+        if hasattr(L, "mte_builder_open_doc_from_summary"):
+            L.mte_builder_open_doc_from_summary.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz,
+                                                            ctypes.POINTER(ctypes.c_uint32)]
         L.mte_builder_error.argtypes = [vp]
         L.mte_builder_error.restype = ctypes.c_char_p
         L.mte_builder_destroy.argtypes = [vp]
@@ -259,6 +263,18 @@ class Builder:
         rc = lib().mte_builder_open_doc(self._h, observer.encode(), ctypes.byref(d))
         if rc:
             raise MteError(f"mte_builder_open_doc: {rc}: {lib().mte_builder_error(self._h).decode()}")
+        return d.value
+
+    def open_doc_from_summary(self, summary, observer="__observer__"):
+        """An open document whose log starts with a SnapshotV1 summary's records (ITree JSON text or
+        dict; Client.load, then applyMsg through append()). Returns its index."""
+        t = summary if isinstance(summary, (str, bytes)) else json.dumps(summary, separators=(",", ":"),
+                                                                          ensure_ascii=False)
+        s = t.encode() if isinstance(t, str) else t
+        d = ctypes.c_uint32()
+        rc = lib().mte_builder_open_doc_from_summary(self._h, observer.encode(), s, len(s), ctypes.byref(d))
+        if rc:
+            raise MteError(f"mte_builder_open_doc_from_summary: {rc}: {lib().mte_builder_error(self._h).decode()}")
         return d.value
 
     def append(self, doc, messages):
@@ -485,8 +501,11 @@ class MergeTreeClient:
     (client.ts:805-836): messages are parsed onto an open builder document as they come, and a read
     (getText, getLength, snapshot) after new messages replays on the GPU only the ops since the last
     read, continuing the document's state from the previous pass (mte_retain). Without new messages
-    a read reuses the last results. A document the row engines cannot hold (summary loads, relative
-    positions, 64+ clients, ...) replays from its first op instead: same results, not incremental."""
+    a read reuses the last results. That holds for a document the row engines cannot hold too (loaded
+    from a summary with load(), relative positions, 64+ clients, '\\n' beside properties): the block
+    engine continues it from a block checkpoint. Still replayed from its first op at every read: a
+    document over the engine's "ck_blk_budget_mb" option, and one after k_solo's LDS fallback or a host
+    re-run."""
 
     def __init__(self, observer="__observer__", device=0):
         self.observer = observer
@@ -496,10 +515,22 @@ class MergeTreeClient:
         self._engine = None
         self._device = device
         self._dirty = True
+        self._started = False
         self.replays = 0  # passes run (a read after new messages runs one)
+
+    def load(self, summary):
+        """Client.load (client.ts:944): start from a SnapshotV1 summary (ITree JSON text or dict)
+        instead of an empty document. Valid before the first message and the first read."""
+        if self._started or self._engine is not None:
+            raise MteError("load() after the first message or read")
+        self._builder = Builder()
+        self._doc = self._builder.open_doc_from_summary(summary, self.observer)
+        self._started = True
+        self._dirty = True
 
     def applyMsg(self, msg):  # noqa: N802 (reference name)
         self._pending.append(msg)
+        self._started = True
         self._dirty = True
 
     def _run(self):
@@ -520,8 +551,10 @@ class MergeTreeClient:
         return self._engine
 
     def resumed_ops(self):
-        """Op records the last read did not replay again (continued from the previous pass)."""
-        return self._run().get_info("resumed_ops")
+        """Op records the last read did not replay again (continued from the previous pass, by the
+        row engines or by the block engine)."""
+        e = self._run()
+        return e.get_info("resumed_ops") + e.get_info("resumed_ops_blk")
 
     def getText(self):  # noqa: N802
         return self._run().text(0)

@@ -264,7 +264,12 @@ int mte_replay(mte_engine* e, mte_stats* out);
 /* Incremental replay (Client.applyMsg is incremental, client.ts:805-836): on = 1 keeps each document's
  * replay state after every mte_replay, so the next mte_load of logs that EXTEND the last pass's (the
  * same documents, each log the old one plus new messages; the engine checks the prefix) replays only
- * the new ops of every document the row engines held; any other document replays from op 0. The
+ * the new ops of every document: the ones the row engines held from their row checkpoints, and the
+ * ones they cannot hold (loaded from a summary, relative positions, 64 or more clients in the window,
+ * '\n' beside properties, local edits) from block checkpoints, up to option "ck_blk_budget_mb" (1024)
+ * of them per pass, shortest documents first. Still from op 0 on every pass: a batch that needs the
+ * extended engine level (a legacy snapshot with catch-up records, SharedMatrix vectors), a document
+ * after k_solo's LDS fallback or a host re-run, and one whose checkpoint did not fit. The
  * results are the full replay's either way. on = 0 drops the kept state. Off by default: a replay
  * of the same batch again would otherwise only re-read its results. */
 int mte_retain(mte_engine* e, int on);
@@ -390,6 +395,11 @@ int mte_builder_add_matrix_from_summary(mte_builder* b, const char* observer_nam
  * document whose log extends the last pass's from that pass's state (replaying only the new ops). */
 int mte_builder_open_doc(mte_builder* b, const char* observer_name, uint32_t* doc);
 int mte_builder_append_messages(mte_builder* b, uint32_t doc, const char* json, size_t len);
+/* Client.load then Client.applyMsg: an open document whose log starts with the records of a SnapshotV1
+ * summary (the ITree JSON mte_builder_add_doc_from_summary takes); mte_builder_append_messages
+ * extends it as it does any open document. */
+int mte_builder_open_doc_from_summary(mte_builder* b, const char* observer_name, const char* summary,
+                                      size_t summary_len, uint32_t* doc);
 int mte_builder_batch(mte_builder* b, mte_batch* out);   /* view valid until destroy */
 const char* mte_builder_error(const mte_builder* b);
 void mte_builder_destroy(mte_builder* b);

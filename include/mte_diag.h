@@ -23,9 +23,14 @@ int mte_run_info(mte_engine* e, uint32_t* spilled, double* lds_ms, double* hbm_m
  * 1 no free HBM slot, 2 the slot too small for its state, 3 no pool row held, 4 the pool full inside
  * an op, 5 the shared-pool route (no in-pass continuation). "resumed_docs" / "resumed_ops" /
  * "ck_offered": with mte_retain, documents the last pass continued from a checkpoint, the op records
- * they did not replay again, and documents whose log extended the previous pass's. */
+ * they did not replay again, and documents whose log extended the previous pass's ("resumed_docs" /
+ * "resumed_ops": the row engines only). "resumed_docs_blk" / "resumed_ops_blk" (64-bit): the same
+ * for the documents the block engine continued (k_blk_ck: summary loads, relative positions, 64+
+ * clients, ...); "ck_blk_saved": block checkpoints the pass wrote; "ck_blk_skipped": such documents
+ * over "ck_blk_budget_mb", which replay from op 0. */
 int mte_get_info(mte_engine* e, const char* key, int64_t* value);
-/* Tuning: "force_hbm", "pool_limit", "hbm_waves_per_cu", "slot_budget_mb"; "retain" = mte_retain. */
+/* Tuning: "force_hbm", "pool_limit", "hbm_waves_per_cu", "slot_budget_mb"; "retain" = mte_retain;
+ * "ck_blk_budget_mb" (1024): the block checkpoint regions of one pass, admitted shortest document first. */
 int mte_set_option(mte_engine* e, const char* key, int64_t value);
 /* Phase cycle counters (profiling build only): PROF_SLOTS u64 per document. */
 int mte_profile(mte_engine* e, uint64_t* out, size_t cap);

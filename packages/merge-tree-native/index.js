@@ -52,8 +52,13 @@ class BatchedMergeEngine {
     /** mte_retain: keep each document's state after a replay, so replaying logs that extend the last
      *  pass's replays only their new ops (Client.applyMsg's incremental cost, client.ts:805-836). */
     retain(on = true) { this._idle(); addon.retain(this._engine, on); }
-    /** op records the last replay did not replay again (continued from the pass before) */
-    resumedOps() { this._idle(); return addon.getInfo(this._engine, "resumed_ops"); }
+    /** op records the last replay did not replay again (continued from the pass before): the row
+     *  engines' ("resumed_ops") plus the block engine's ("resumed_ops_blk": documents loaded from a
+     *  summary, with relative positions, 64+ clients, ...) */
+    resumedOps() {
+        this._idle();
+        return addon.getInfo(this._engine, "resumed_ops") + addon.getInfo(this._engine, "resumed_ops_blk");
+    }
     /** mte_get_info: routing and counters of the last pass ("resumed_docs", "rows", "solo", ...) */
     getInfo(key) { this._idle(); return addon.getInfo(this._engine, key); }
     generate(kind, nDocs, nOps, nClients = 8, seed = 0) {
@@ -123,8 +128,13 @@ function parseSummaries(buf) {
  * parses the staged messages onto the document's open log (builderAppendMessages) and replays on the
  * GPU only the ops since the previous read, continuing the document's state from that pass (the
  * engine's retain mode, mte_retain). Reads without new messages reuse the last results. A document
- * loaded from a summary, or one the row engines cannot hold (relative positions, 64+ clients, ...),
- * replays from its first op on each read instead: the same results, not incremental.
+ * the row engines cannot hold (loaded from a summary, relative positions, 64+ clients, ...) is
+ * continued by the block engine from a block checkpoint. After load(summary) each read stages the
+ * summary and the whole suffix again (host work linear in the log); the engine's prefix check finds
+ * the log an extension of the last read's, so the GPU still replays only the new messages. Still
+ * replayed from its first op at each read: a document over the engine's "ck_blk_budget_mb" option, a
+ * client with newMergeTreeSnapshotFormat false whose log has catch-up messages (the legacy snapshot's
+ * delta records), and a document after k_solo's LDS fallback or a host re-run.
  */
 class MergeTreeClient {
     constructor(observer = "__observer__", options = {}) {
@@ -159,7 +169,7 @@ class MergeTreeClient {
             this._engine = new BatchedMergeEngine(this.options);
             addon.retain(this._engine._engine, true);
         }
-        if (this.summary !== undefined) {  // SnapshotLoader + suffix: a whole replay per read
+        if (this.summary !== undefined) {  // SnapshotLoader + suffix, staged whole per read (the replay continues)
             for (const m of this.pending) this.messages.push(m);
             this.pending = [];
             this._engine.load([{ observer: this.observer, messages: this.messages.slice(), summary: this.summary }]);
