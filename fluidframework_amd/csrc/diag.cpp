@@ -71,7 +71,7 @@ int mte_set_option(mte_engine* e, const char* key, int64_t value) {
     else if (k == "rows_mixed") e->rows_mixed = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2);
     else if (k == "retain") {  // incremental replay: checkpoints kept for a later pass over extended logs
         e->retain = value != 0;
-        if (!e->retain) ck_forget(e);
+        if (!e->retain) e->ck.reset();
     }
     // block checkpoint regions of one checkpoint buffer (documents over it replay from op 0 every pass)
     else if (k == "ck_blk_budget_mb") e->ck_blk_budget = (uint64_t)std::max<int64_t>(0, value) << 20;

@@ -1,7 +1,7 @@
 // engine_host.hpp — what the engine's host units share: the engine object of include/mte.h's
 // mte_engine, its device buffers, the error helpers, and the few functions that cross units
-// (engine_load.cpp, engine_run.cpp, readback.cpp, gather.cpp, diag.cpp). Host-only: no kernel includes
-// it.
+// (engine_load.cpp, engine_run.cpp, engine_ckpt.cpp, readback.cpp, gather.cpp, diag.cpp). Host-only: no
+// kernel includes it.
 //
 // Everything declared here is internal to libmte.so (hidden visibility); struct mte_engine keeps the
 // visibility include/mte.h declares it with.
@@ -12,9 +12,11 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/mte.h"
+#include "ck_plan.hpp"
 #include "engine_types.hpp"
 #include "host_batch.hpp"
 
@@ -39,6 +41,46 @@ struct DevBuf {
     // allocates nothing (hipFree + hipMalloc of the multi-GB tables took 2.7-3.0 s on some loads,
     // profiles/pcie_r03m_c4.json)
     hipError_t fit(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count); }
+};
+
+// A property-map table of one pass beside the load-time one (d_maps): the listed documents ran in
+// per-document HBM regions with worst-case tables of their own (layout_hbm_docs), read back from here.
+struct MapSide {
+    DevBuf<uint32_t> d;
+    std::vector<uint64_t> off;  // per document: its first record, UINT64_MAX = its maps are not in this table
+    std::vector<uint32_t> cap;
+    void clear() { off.clear(); }
+    bool has(uint32_t doc) const { return doc < off.size() && off[doc] != UINT64_MAX; }
+    void set(uint32_t n_docs, const std::vector<uint32_t>& list, const std::vector<DocCfg>& cfg) {
+        off.assign(n_docs, UINT64_MAX);
+        cap.assign(n_docs, 0);
+        for (uint32_t doc : list) {
+            off[doc] = cfg[doc].map_off;
+            cap[doc] = cfg[doc].map_cap;
+        }
+    }
+};
+
+// What layout_hbm_docs laid out: the sizes of the two buffers, and the load-time (map_off, map_cap) of
+// its documents, put back in the engine's cfg by restore() or when the layout goes out of scope,
+// whichever comes first (the next pass starts from the load-time layout, however this one ends).
+struct HbmDocLayout {
+    uint64_t bytes = 0, maps = 0;  // the HBM regions, and the map table's records
+    HbmDocLayout() = default;
+    HbmDocLayout(const HbmDocLayout&) = delete;
+    HbmDocLayout& operator=(const HbmDocLayout&) = delete;
+    ~HbmDocLayout() { restore(); }
+    void restore() {
+        for (size_t q = 0; q < docs.size(); q++) {
+            (*cfg)[docs[q]].map_off = keep[q].first;
+            (*cfg)[docs[q]].map_cap = keep[q].second;
+        }
+        docs.clear();
+        keep.clear();
+    }
+    std::vector<DocCfg>* cfg = nullptr;
+    std::vector<uint32_t> docs;
+    std::vector<std::pair<uint64_t, uint32_t>> keep;
 };
 #pragma GCC visibility pop
 
@@ -145,10 +187,7 @@ struct mte_engine {
     DevBuf<uint32_t> d_solo_started;  // k_solo_gate's counter
     DevBuf<uint32_t> d_rows_retry;    // k_rows' restart queue (Params::rows_retry)
     DevBuf<uint32_t> d_rows_cont;     // k_rows' continuation records (Params::rows_cont), one per slot
-    // property maps of the documents the host re-ran (their worst-case table), by document
-    DevBuf<uint32_t> d_maps_rr;
-    std::vector<uint64_t> map_rr_off;  // UINT64_MAX = the document's maps are in d_maps
-    std::vector<uint32_t> map_rr_cap;
+    MapSide maps_rr;  // property maps of the documents the host re-ran (rerun_spilled)
     DevBuf<DocCfg> d_cfg;
     DevBuf<DocRes> d_res;
     DevBuf<uint4> d_out_vis, d_out_aux;
@@ -187,19 +226,7 @@ struct mte_engine {
     // leave every finished document's state in a checkpoint region; a pass over a batch whose logs
     // extend the last pass's (ck_match) continues each such document from its checkpoint
     DevBuf<uint32_t> d_ck[2];
-    int ck_cur = -1;  // the buffer with the last pass's checkpoints (-1: none)
-    struct CkDoc {
-        uint64_t n_ops = 0, n_pay = 0, off = 0, h_ops = 0, h_pay = 0;
-        uint8_t kind = 0;  // the region's format: 0 a row checkpoint, 1 a block checkpoint (k_blk_ck)
-        uint8_t props = 0; // the log has an op with a property set (its map records hold key / value ids)
-        uint64_t cap = 0;  // words of the region
-    };
-    std::vector<CkDoc> ck_prev;        // per document of the last pass: what its checkpoint covers, and where
-    std::vector<CkDoc> ck_load;        // per document of the loaded batch: its whole log's hashes
-    std::vector<uint64_t> ck_match;    // per document of the loaded batch: op records it shares with ck_prev
-    HostBatch ck_tabs;                 // the last pass's property tables (ids must keep their meaning)
-    uint64_t ck_tabs_n = 0;            // their key / value / propset counts, 0 = none kept
-    uint32_t ck_map_words = 0;
+    CkState ck;  // what is kept of the last pass's (ck_plan.hpp)
     // block documents of a retained pass (engine level <= 1): the documents the row engines cannot
     // replay (doc_not_rows) and those whose offered checkpoint is a block checkpoint run on k_blk_ck
     // (mte_ckpt.hip), each in an HBM region and a worst-case map table of its own, and are taken out of
@@ -209,10 +236,10 @@ struct mte_engine {
     std::vector<uint8_t> blk_ck;             // per document: 1 = on blk_list (writes a block checkpoint this pass),
                                              // 2 = a block document over the budget (no checkpoint), 0 = neither
     DevBuf<unsigned char> d_hbm_blk;         // their HBM regions (d_hbm is the re-run's, reallocated per pass)
-    DevBuf<uint32_t> d_maps_blk, d_blk_list, d_blk_saved;
-    std::vector<uint64_t> map_blk_off;       // UINT64_MAX = the document's maps are not in d_maps_blk
-    std::vector<uint32_t> map_blk_cap;
-    bool d_order_stale = false;              // d_order holds a pass's reduced list, not e->order
+    MapSide maps_blk;                        // their property maps
+    DevBuf<uint32_t> d_blk_list, d_blk_saved;
+    bool d_order_stale = false;              // d_order / d_cfg hold a pass's reduced list and map tables, not
+                                             // e->order / e->cfg
     hipEvent_t ev_blk = nullptr;             // k_blk_ck done (second stream)
 
     // ---- last load and last run
@@ -291,8 +318,7 @@ int upload(mte_engine* e, DevBuf<T>& d, const std::vector<T>& h) {
 uint32_t solo_count(const mte_engine* e);
 void wave_plan(const mte_engine* e, uint32_t nd, uint32_t& groups, uint32_t& hbm_waves, uint32_t* lds_active = nullptr,
                uint32_t n_solo = 0);
-void ck_forget(mte_engine* e);
-int ck_match_batch(mte_engine* e, const mte_batch* b);
+int layout_hbm_docs(mte_engine* e, bool gen, const std::vector<uint32_t>& list, HbmDocLayout& lay);
 int run_kernel(mte_engine* e, bool gen);
 // Every device read of the read-back (readback.cpp makes no HIP call) and of the diagnostics: each is
 // one blocking hipMemcpy, except the two downloads, which copy once per replay.
@@ -303,5 +329,28 @@ int fetch_map_record(mte_engine* e, uint32_t d, uint32_t id, uint32_t* w);
 int fetch_handle_table(mte_engine* e, uint32_t d, std::vector<uint32_t>& w);
 int fetch_cell_handles(mte_engine* e, std::vector<uint32_t>& h);
 int fetch_catch_up_records(mte_engine* e, uint32_t d, std::vector<uint4>& rec);
+
+// ---- engine_ckpt.cpp: the device half of incremental replay (option retain; ck_plan.hpp is the other)
+int ck_match_batch(mte_engine* e, const mte_batch* b);  // mte_load: which documents continue
+// e->order for the length of a retained pass that runs without its block documents, and their layout:
+// both put back when the pass ends, however it ends (d_order and d_cfg are uploaded again by the next pass)
+struct BlkGuard {
+    mte_engine* e;
+    std::vector<uint32_t> all;
+    HbmDocLayout lay;
+    bool on = false;
+    ~BlkGuard() {
+        if (on) e->order.swap(all);
+    }
+};
+// run_kernel's calls, in its order: plan the pass's block documents (on: a retained pass at level <= 1)
+// and take them out of e->order; k_blk_ck's buffers, before the pass's first event; the pass's regions
+// (Params::ck_out / ck_in); k_blk_ck on s_blk beside the bulk, joined into s_main; after the pass, its
+// checkpoints become the ones the next pass continues from (ctr: the pass's device counters).
+int ck_blk_plan(mte_engine* e, bool on, BlkGuard& g);
+int ck_blk_setup(mte_engine* e, const BlkGuard& g, hipStream_t s);
+int ck_begin(mte_engine* e);
+int ck_blk_launch(mte_engine* e, int full, hipStream_t s_blk, hipStream_t s_main);
+int ck_end(mte_engine* e, const uint32_t* ctr);
 
 #pragma GCC visibility pop

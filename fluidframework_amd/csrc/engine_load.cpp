@@ -605,7 +605,7 @@ int mte_load(mte_engine* e, const mte_batch* b) {
     e->ext_needed = ext;
     if ((rc = alloc_out_text(e))) return rc;
     if (e->retain) return ck_match_batch(e, b);
-    ck_forget(e);
+    e->ck.reset();
     return MTE_OK;
 }
 
@@ -645,7 +645,7 @@ int mte_generate_ids(mte_engine* e, uint32_t kind, uint32_t n_docs, uint32_t n_o
     e->map_words = MAP_WORDS;  // the generator's property sets hold at most four keys
     if (kind != 2 && kind != 3 && kind != 5) return set_err(e, MTE_E_ARG, "generator kind must be 2, 3 or 5");
     HIP_TRY(e, hipSetDevice(e->device));
-    ck_forget(e);  // (a new batch: no checkpoint of the last one may be continued)
+    e->ck.reset();  // (a new batch: no checkpoint of the last one may be continued)
     e->hb = HostBatch();
     uint32_t nps = build_generator_props(e);
     std::vector<uint64_t> nops(n_docs), pay(n_docs), pi(n_docs), an(n_docs);

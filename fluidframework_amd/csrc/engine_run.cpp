@@ -1,8 +1,8 @@
 // engine_run.cpp — the replay pass: mte_replay / mte_retain of include/mte.h.
 //   * one wavefront per document on the GPU (mte_kernels.hip / engine.hpp): an LDS-resident pass over
 //     every document, then an HBM-resident pass for the documents that outgrew the LDS plan.
-//   * the wave plan and routing of a pass, incremental replay (checkpoints), SnapshotV1 emission
-//     (emit.hip) in two rounds around the critical path.
+//   * the wave plan and routing of a pass, SnapshotV1 emission (emit.hip) in two rounds around the
+//     critical path; incremental replay (option retain) is engine_ckpt.cpp's, called from run_kernel.
 //   * every device read of the results: the downloads and fetchers readback.cpp and diag.cpp call.
 #include <hip/hip_runtime.h>
 
@@ -91,274 +91,6 @@ uint32_t solo_count(const mte_engine* e) {
         k++;
     }
     return k;
-}
-
-// ---------------------------------------------------------------- incremental replay (option retain)
-void ck_forget(mte_engine* e) {
-    e->ck_cur = -1;
-    e->ck_prev.clear();
-    e->ck_load.clear();
-    e->ck_match.clear();
-    e->ck_tabs_n = 0;
-}
-// word-wise hash of a byte range, continuing from h (a prefix's hash continues to the whole log's)
-static uint64_t ck_hash(uint64_t h, const void* p, size_t n) {
-    const unsigned char* b = (const unsigned char*)p;
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        uint64_t w;
-        memcpy(&w, b + i, 8);
-        h = (h ^ w) * 0x9E3779B97F4A7C15ull;
-        h ^= h >> 29;
-    }
-    for (; i < n; i++) h = (h ^ b[i]) * 0x100000001B3ull;
-    return h;
-}
-// payload units one at a time: a prefix's hash continued over the rest is the whole run's hash
-// whatever the prefix's length (a word-wise hash would regroup the units after an odd cut)
-static uint64_t ck_hash_units(uint64_t h, const uint16_t* y, uint64_t n) {
-    for (uint64_t i = 0; i < n; i++) {
-        h = (h ^ y[i]) * 0x100000001B3ull;
-        h ^= h >> 31;
-    }
-    return h;
-}
-// an op record as the engine reads it: MTE_F_CATCHUP marks the ops of the messages still above
-// minSeq at the END of a log (DocBuild::commit), which the row engines never read, so a prefix log
-// and its extension differ there and nowhere else.
-// A property-set id is hashed as the set's content (ps_hash: its keys' and values' interned texts in
-// order), not as the number a builder happened to give it: a fresh builder over longer logs of several
-// property-carrying documents numbers keys, values and sets in another order, and the log is the
-// same log. (Cell records' props is a value id of another table walk: hashed as it is.)
-static uint64_t ck_hash_ops(uint64_t h, const mte_op* o, uint64_t n, const std::vector<uint64_t>& ps_hash, bool* props = nullptr) {
-    for (uint64_t i = 0; i < n; i++) {
-        mte_op x = o[i];
-        x.flags &= ~MTE_F_CATCHUP;
-        const bool set = x.props && x.props < ps_hash.size() && x.type != MTE_OP_CELL &&
-                         !(x.type == MTE_OP_NOOP && (x.flags & MTE_F_MX_MASK));
-        const uint64_t ph = set ? ps_hash[x.props] : 0;
-        if (set) {
-            x.props = 1;
-            if (props) *props = true;
-        }
-        h = ck_hash(h, &x, sizeof x);
-        if (set) {
-            h = (h ^ ph) * 0x9E3779B97F4A7C15ull;
-            h ^= h >> 29;
-        }
-    }
-    return h;
-}
-// content hash of every property set of a batch's tables
-static std::vector<uint64_t> ck_ps_hashes(const HostBatch& t) {
-    std::vector<uint64_t> out(t.propsets.size(), 0);
-    for (size_t s = 0; s < t.propsets.size(); s++) {
-        uint64_t h = 0xCBF29CE484222325ull;
-        const mte_propset& ps = t.propsets[s];
-        for (uint32_t q = 0; q < ps.count && (size_t)ps.first + q < t.prop_keys.size(); q++) {
-            const uint32_t k = t.prop_keys[ps.first + q], v = t.prop_vals[ps.first + q];
-            auto mix = [&](const std::string& text, const std::vector<uint64_t>& off, uint32_t id, unsigned char sep) {
-                if ((size_t)id + 1 < off.size())
-                    for (uint64_t c = off[id]; c < off[id + 1]; c++) h = (h ^ (unsigned char)text[c]) * 0x100000001B3ull;
-                h = (h ^ sep) * 0x100000001B3ull;
-            };
-            mix(t.key_text, t.key_offsets, k, 0xFF);
-            mix(t.val_text, t.val_offsets, v, 0xFE);
-        }
-        out[s] = h ^ ((uint64_t)ps.count << 56);
-    }
-    return out;
-}
-static uint64_t ck_tabs_count(const HostBatch& t) {
-    return (uint64_t)t.propsets.size() + t.prop_keys.size() + t.key_offsets.size() + t.val_offsets.size();
-}
-// the loaded tables start with the last pass's: every id the checkpointed map records hold means the
-// same key / value / property set
-static bool ck_tabs_extend(const HostBatch& old, const HostBatch& nw) {
-    auto pre = [](const auto& a, const auto& b) { return a.size() <= b.size() && std::equal(a.begin(), a.end(), b.begin()); };
-    auto pre_ps = [](const std::vector<mte_propset>& a, const std::vector<mte_propset>& b) {
-        if (a.size() > b.size()) return false;
-        for (size_t i = 0; i < a.size(); i++)
-            if (a[i].first != b[i].first || a[i].count != b[i].count) return false;
-        return true;
-    };
-    return pre_ps(old.propsets, nw.propsets) && pre(old.prop_keys, nw.prop_keys) && pre(old.prop_vals, nw.prop_vals) &&
-           pre(old.key_offsets, nw.key_offsets) && pre(old.key_text, nw.key_text) && pre(old.val_offsets, nw.val_offsets) &&
-           pre(old.val_text, nw.val_text);
-}
-// the loaded batch's tables are the ones the kept checkpoints' ids mean
-static void ck_keep_tabs(mte_engine* e) {
-    e->ck_tabs.propsets = e->hb.propsets;
-    e->ck_tabs.prop_keys = e->hb.prop_keys;
-    e->ck_tabs.prop_vals = e->hb.prop_vals;
-    e->ck_tabs.key_offsets = e->hb.key_offsets;
-    e->ck_tabs.key_text = e->hb.key_text;
-    e->ck_tabs.val_offsets = e->hb.val_offsets;
-    e->ck_tabs.val_text = e->hb.val_text;
-    e->ck_tabs_n = 1 + ck_tabs_count(e->hb);
-    e->ck_map_words = e->map_words;
-}
-// mte_load with retain: which documents of the batch extend the last pass's (ck_match), and the
-// hashes of their whole logs for the next one.
-// Tables that do not start with the last pass's (a fresh builder per pass over several
-// property-carrying documents interns in another order) still number the same keys and values: a
-// document without property sets has no id in its checkpoint and continues as it is; a block
-// checkpoint's map records are renumbered in place, once, to the loaded batch's ids (k_ck_xlate), and
-// the kept tables become the loaded ones. A row checkpoint with map records is not offered then.
-int ck_match_batch(mte_engine* e, const mte_batch* b) {
-    const uint32_t nd = b->n_docs;
-    e->ck_match.assign(nd, 0);
-    e->ck_load.assign(nd, mte_engine::CkDoc{});
-    const bool kept = e->ck_cur >= 0 && e->ck_prev.size() == nd && e->ck_tabs_n && e->ck_map_words == e->map_words;
-    const bool extend = kept && ck_tabs_extend(e->ck_tabs, e->hb);
-    const std::vector<uint64_t> ps_hash = ck_ps_hashes(e->hb);
-    for (uint32_t d = 0; d < nd; d++) {
-        const mte_op* o = b->ops + b->doc_op_offsets[d];
-        const uint16_t* y = b->payload + b->doc_payload_offsets[d];
-        const uint64_t n = b->doc_op_offsets[d + 1] - b->doc_op_offsets[d];
-        const uint64_t np = b->doc_payload_offsets[d + 1] - b->doc_payload_offsets[d];
-        mte_engine::CkDoc& c = e->ck_load[d];
-        c.n_ops = n;
-        c.n_pay = np;
-        uint64_t ho = 0xCBF29CE484222325ull, hp = 0xCBF29CE484222325ull, k = 0, kp = 0;
-        bool has_props = false;
-        if (kept) {
-            const mte_engine::CkDoc& q = e->ck_prev[d];
-            if (q.n_ops && q.n_ops <= n && q.n_pay <= np) {
-                ho = ck_hash_ops(ho, o, q.n_ops, ps_hash, &has_props);
-                hp = ck_hash_units(hp, y, q.n_pay);
-                k = q.n_ops;
-                kp = q.n_pay;
-                if (ho == q.h_ops && hp == q.h_pay && (extend || !q.props || q.kind == 1)) e->ck_match[d] = q.n_ops;
-            }
-        }
-        c.h_ops = ck_hash_ops(ho, o + k, n - k, ps_hash, &has_props);
-        c.h_pay = ck_hash_units(hp, y + kp, np - kp);
-        c.props = has_props;
-    }
-    if (!kept || extend) return MTE_OK;
-    // renumber the offered block checkpoints that hold ids; every other kept checkpoint with ids is in
-    // the old numbering still and is dropped, since the kept tables become this batch's
-    const HostBatch& old = e->ck_tabs;
-    auto xlate = [](const std::string& ot, const std::vector<uint64_t>& oo, const std::string& nt, const std::vector<uint64_t>& no) {
-        std::unordered_map<std::string, uint32_t> ids;
-        for (size_t i = 0; i + 1 < no.size(); i++) ids.emplace(nt.substr(no[i], no[i + 1] - no[i]), (uint32_t)i);
-        std::vector<uint32_t> x(oo.empty() ? 0 : oo.size() - 1, NONE);
-        for (size_t i = 0; i + 1 < oo.size(); i++) {
-            auto it = ids.find(ot.substr(oo[i], oo[i + 1] - oo[i]));
-            if (it != ids.end()) x[i] = it->second;
-        }
-        return x;
-    };
-    const std::vector<uint32_t> key_xl = xlate(old.key_text, old.key_offsets, e->hb.key_text, e->hb.key_offsets);
-    const std::vector<uint32_t> val_xl = xlate(old.val_text, old.val_offsets, e->hb.val_text, e->hb.val_offsets);
-    std::vector<uint64_t> off, cap;
-    for (uint32_t d = 0; d < nd; d++) {
-        mte_engine::CkDoc& q = e->ck_prev[d];
-        if (!q.props) continue;
-        if (e->ck_match[d] && q.kind == 1 && q.cap) {
-            off.push_back(q.off);
-            cap.push_back(q.cap);
-        } else {
-            e->ck_match[d] = 0;
-            q.n_ops = 0;  // (never offered again)
-        }
-    }
-    if (!off.empty()) {
-        DevBuf<uint64_t> d_off, d_cap;
-        DevBuf<uint32_t> d_kx, d_vx;
-        HIP_TRY(e, d_off.alloc(off.size()));
-        HIP_TRY(e, d_cap.alloc(cap.size()));
-        HIP_TRY(e, d_kx.alloc(key_xl.size()));
-        HIP_TRY(e, d_vx.alloc(val_xl.size()));
-        HIP_TRY(e, hipMemcpy(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_cap.p, cap.data(), cap.size() * 8, hipMemcpyHostToDevice));
-        if (!key_xl.empty()) HIP_TRY(e, hipMemcpy(d_kx.p, key_xl.data(), key_xl.size() * 4, hipMemcpyHostToDevice));
-        if (!val_xl.empty()) HIP_TRY(e, hipMemcpy(d_vx.p, val_xl.data(), val_xl.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(e, launch_ck_xlate(e->d_ck[e->ck_cur].p, d_off.p, d_cap.p, (uint32_t)off.size(), d_kx.p, (uint32_t)key_xl.size(),
-                                   d_vx.p, (uint32_t)val_xl.size(), e->map_words, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-    }
-    ck_keep_tabs(e);
-    return MTE_OK;
-}
-// the previous pass left document d a checkpoint (in a region of its own) that this pass's log extends
-static bool ck_have(const mte_engine* e, uint32_t d) {
-    return e->ck_cur >= 0 && d < e->ck_match.size() && d < e->ck_prev.size() && e->ck_match[d] && e->ck_prev[d].cap;
-}
-// run_kernel with retain: this pass's regions, the previous pass's ones to continue from.
-// The row regions first, then the block documents' (e->blk_ck: sized from the capacities of the engine
-// each runs on, cfg's hb_* and its worst-case map_cap). A checkpoint of the other kind than the
-// engine the document runs on this pass is not offered: the document replays from op 0.
-static int ck_begin(mte_engine* e) {
-    const uint32_t nd = (uint32_t)e->cfg.size();
-    const int out = e->ck_cur == 0 ? 1 : 0;
-    uint64_t tot = 0, row_tot = 0;
-    e->last_ck_offered = 0;
-    for (int blk = 0; blk < 2; blk++) {
-        for (uint32_t d = 0; d < nd; d++) {
-            DocCfg& c = e->cfg[d];
-            const bool is_blk = d < e->blk_ck.size() && e->blk_ck[d] == 1;
-            if (is_blk != (blk == 1)) continue;
-            c.ck_out_off = tot;
-            c.ck_cap = is_blk ? blk_ck_region_words(c.hb_blk, c.hb_ord, c.hb_in, c.hb_heap, c.seg_cap, c.ovl2_off != OVL2_NONE,
-                                                    c.arena_cap, c.map_cap, e->map_words)
-                              : ck_region_words(c.arena_cap, c.map_cap, e->map_words);
-            if (d < e->blk_ck.size() && e->blk_ck[d] == 2) c.ck_cap = 0;  // a block document over the budget
-            tot += (c.ck_cap + 63) & ~63ull;
-            const bool have = ck_have(e, d);
-            const bool use = have && (e->ck_prev[d].kind == 1) == is_blk;
-            c.ck_at = use ? e->ck_match[d] : 0;
-            c.ck_in_off = use ? e->ck_prev[d].off : 0;
-            e->last_ck_offered += have;
-        }
-        if (!blk) row_tot = tot;
-    }
-    HIP_TRY(e, e->d_ck[out].fit(std::max<uint64_t>(tot, 64)));
-    // every row region invalid until saved; k_blk_ck_clear clears the block regions' header words
-    HIP_TRY(e, hipMemsetAsync(e->d_ck[out].p, 0, row_tot * 4, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_cfg.p, e->cfg.data(), nd * sizeof(DocCfg), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    e->P.ck_out = e->d_ck[out].p;
-    e->P.ck_in = e->ck_cur >= 0 ? e->d_ck[e->ck_cur].p : nullptr;
-    return MTE_OK;
-}
-// after the pass: its checkpoints are the ones the next pass continues from (the same batch replayed
-// again continues every document from its end)
-static int ck_end(mte_engine* e, const uint32_t* ctr) {
-    const uint32_t nd = (uint32_t)e->cfg.size();
-    e->ck_cur = e->ck_cur == 0 ? 1 : 0;
-    e->ck_prev.assign(nd, mte_engine::CkDoc{});
-    for (uint32_t d = 0; d < nd; d++) {
-        mte_engine::CkDoc& q = e->ck_prev[d];
-        if (d < e->ck_load.size()) q = e->ck_load[d];
-        q.off = e->cfg[d].ck_out_off;
-        q.n_ops = e->n_ops_doc[d];
-        q.n_pay = e->cfg[d].payload_len;
-        // a block checkpoint: k_blk_ck's, or that of a document that left its rows mid-pass and finished in
-        // the checkpointing k_rows_cont (DocRes mode 6; it stays a block document from the next pass on)
-        q.kind = d < e->blk_ck.size() && e->blk_ck[d] == 1;
-        q.cap = e->cfg[d].ck_cap;
-        if (!q.cap) q.n_ops = 0;  // no region (over the block budget): nothing to offer
-        if (!q.kind && q.cap && d < e->res.size() && e->res[d].mode == 6 && e->res[d].status == 0) {
-            // (its region is a row region: the state fitted if the valid word is there; else nothing was
-            // saved and the document stays a row document)
-            uint32_t magic = 0;
-            HIP_TRY(e, hipMemcpy(&magic, e->P.ck_out + q.off, sizeof magic, hipMemcpyDeviceToHost));
-            q.kind = magic == BCK_MAGIC;
-            e->last_ck_blk_saved += q.kind;
-        }
-    }
-    e->ck_match.assign(nd, 0);
-    for (uint32_t d = 0; d < nd; d++) e->ck_match[d] = e->ck_prev[d].n_ops;
-    ck_keep_tabs(e);
-    e->last_resumed_docs = ctr[12];
-    e->last_resumed_ops = ctr[13];
-    e->last_resumed_docs_blk = ctr[3];
-    e->last_resumed_ops_blk = (uint64_t)ctr[14] | ((uint64_t)ctr[15] << 32);
-    e->P.ck_out = nullptr;
-    e->P.ck_in = nullptr;
-    return MTE_OK;
 }
 
 // HBM-resident capacities for a document that outgrew the LDS plan (blocks hold >= 4 segments
@@ -613,17 +345,17 @@ static int solo_timing(mte_engine* e, bool bulk) {
 // The listed documents in per-document HBM regions with worst-case capacities (DocCfg::hb_*, for
 // Engine::bind_hbm) and worst-case property-map tables of their own, for the host's re-run and for the
 // block documents of a retained pass. Sets e->cfg (the caller uploads it): hb_off from 0 in a buffer of
-// `total` bytes, map_off from 0 in a table of `mtot` records; keep_maps gets each document's load-time
-// (map_off, map_cap), which the caller puts back after the pass.
-static int layout_hbm_docs(mte_engine* e, bool gen, const std::vector<uint32_t>& list,
-                           std::vector<std::pair<uint64_t, uint32_t>>& keep_maps, uint64_t& total, uint64_t& mtot) {
-    total = mtot = 0;
-    keep_maps.clear();
+// lay.bytes, map_off from 0 in a table of lay.maps records. lay puts each document's load-time
+// (map_off, map_cap) back (a layout it held before is put back first).
+int layout_hbm_docs(mte_engine* e, bool gen, const std::vector<uint32_t>& list, HbmDocLayout& lay) {
+    lay.restore();
+    lay.cfg = &e->cfg;
+    lay.bytes = lay.maps = 0;
     for (uint32_t d : list) {
         uint64_t bytes;
         doc_hbm_caps(e->n_ops_doc[d], e->cfg[d], bytes);
-        e->cfg[d].hb_off = total;
-        total += (bytes + 255) & ~255ull;
+        e->cfg[d].hb_off = lay.bytes;
+        lay.bytes += (bytes + 255) & ~255ull;
     }
     // property maps: the load-time estimate (prop inserts + 4 per annotate) may be short for such a
     // document; it gets the worst case, a new map per annotated character, in a table of its own
@@ -649,117 +381,44 @@ static int layout_hbm_docs(mte_engine* e, bool gen, const std::vector<uint32_t>&
                     cap += 1;
             }
         }
-        keep_maps.emplace_back(c.map_off, c.map_cap);
+        lay.docs.push_back(d);
+        lay.keep.emplace_back(c.map_off, c.map_cap);
         c.map_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFF0ull);
-        c.map_off = mtot;
-        mtot += c.map_cap;
+        c.map_off = lay.maps;
+        lay.maps += c.map_cap;
     }
     return MTE_OK;
 }
 
 // second pass: the spilled documents, HBM-resident, one wave each, longest first
 static int rerun_spilled(mte_engine* e, bool gen, int full, const std::vector<uint32_t>& spill, float& hbm_ms) {
-    const uint32_t nd = (uint32_t)e->order.size(), nall = e->P.n_docs;
     int rc;
-    uint64_t total = 0, mtot = 0;
-    std::vector<std::pair<uint64_t, uint32_t>> keep_maps;
-    if ((rc = layout_hbm_docs(e, gen, spill, keep_maps, total, mtot))) return rc;
-    HIP_TRY(e, e->d_hbm.alloc(total));
-    // their maps are read back from the re-run table (e->map_rr_off)
-    e->map_rr_off.assign(nall, UINT64_MAX);
-    e->map_rr_cap.assign(nall, 0);
-    for (uint32_t d : spill) {
-        e->map_rr_off[d] = e->cfg[d].map_off;
-        e->map_rr_cap[d] = e->cfg[d].map_cap;
-    }
-    HIP_TRY(e, e->d_maps_rr.alloc(std::max<uint64_t>(mtot, 1) * e->map_words));
+    HbmDocLayout lay;  // (puts e->cfg back on every return)
+    if ((rc = layout_hbm_docs(e, gen, spill, lay))) return rc;
+    HIP_TRY(e, e->d_hbm.alloc(lay.bytes));
+    e->maps_rr.set(e->P.n_docs, spill, e->cfg);  // their maps are read back from the re-run table
+    HIP_TRY(e, e->maps_rr.d.alloc(std::max<uint64_t>(lay.maps, 1) * e->map_words));
+    const bool stale = e->d_order_stale;
+    e->d_order_stale = true;  // (d_cfg holds the re-run's layout until the upload below)
     if ((rc = upload(e, e->d_cfg, e->cfg))) return rc;
     if ((rc = upload(e, e->d_list, spill))) return rc;
-    e->P.docs = e->d_cfg.p;
-    e->P.hbm = e->d_hbm.p;
-    e->P.doc_list = e->d_list.p;
-    e->P.n_list = (uint32_t)spill.size();
-    e->P.maps = e->d_maps_rr.p;
-    e->P.map_rerun = 1;
+    Params p = e->P;
+    p.docs = e->d_cfg.p;
+    p.hbm = e->d_hbm.p;
+    p.doc_list = e->d_list.p;
+    p.n_list = (uint32_t)spill.size();
+    p.maps = e->maps_rr.d.p;
+    p.map_rerun = 1;
     HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
-    HIP_TRY(e, launch_hbm(e->P, gen, full, (uint32_t)spill.size(), e->stream));
+    HIP_TRY(e, launch_hbm(p, gen, full, (uint32_t)spill.size(), e->stream));
     HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     HIP_TRY(e, hipEventElapsedTime(&hbm_ms, e->ev0, e->ev1));
-    e->P.maps = e->d_maps.p;
-    e->P.map_rerun = 0;
-    for (size_t q = 0; q < spill.size(); q++) {  // the next pass starts from the load-time layout
-        e->cfg[spill[q]].map_off = keep_maps[q].first;
-        e->cfg[spill[q]].map_cap = keep_maps[q].second;
-    }
+    lay.restore();  // the next pass starts from the load-time layout
     if ((rc = upload(e, e->d_cfg, e->cfg))) return rc;
-    e->P.docs = e->d_cfg.p;
-    e->P.doc_list = e->d_order.p;
-    e->P.n_list = nd;
+    e->d_order_stale = stale;
     return MTE_OK;
 }
-
-// A retained pass's block documents (engine level <= 1): every document of the pass the row engines
-// cannot replay, and every one whose offered checkpoint is a block checkpoint (a k_rows document that
-// ever became a block document stays one). Lays out their HBM regions and map tables in e->cfg
-// (layout_hbm_docs; keep_maps as there) and admits them to the checkpoint budget shortest first: one
-// whose region does not fit is not listed (e->blk_ck 2) and runs where it runs without retain.
-static int blk_plan(mte_engine* e, std::vector<std::pair<uint64_t, uint32_t>>& keep_maps, uint64_t& total, uint64_t& mtot) {
-    const uint32_t nall = e->P.n_docs;
-    e->blk_list.clear();
-    e->blk_ck.assign(nall, 0);
-    total = mtot = 0;
-    std::vector<uint32_t> cand;
-    for (uint32_t d : e->order)
-        if ((e->doc_not_rows.size() == nall && e->doc_not_rows[d]) || (ck_have(e, d) && e->ck_prev[d].kind == 1)) cand.push_back(d);
-    if (cand.empty()) return MTE_OK;
-    int rc;
-    if ((rc = layout_hbm_docs(e, false, cand, keep_maps, total, mtot))) return rc;
-    std::vector<uint32_t> by_len(cand);
-    std::stable_sort(by_len.begin(), by_len.end(), [&](uint32_t a, uint32_t b) { return e->n_ops_doc[a] < e->n_ops_doc[b]; });
-    uint64_t used = 0;
-    for (uint32_t d : by_len) {
-        const DocCfg& c = e->cfg[d];
-        const uint64_t w = (blk_ck_region_words(c.hb_blk, c.hb_ord, c.hb_in, c.hb_heap, c.seg_cap, c.ovl2_off != OVL2_NONE,
-                                                c.arena_cap, c.map_cap, e->map_words) + 63) & ~63ull;
-        if ((used + w) * 4 <= e->ck_blk_budget) {
-            used += w;
-            e->blk_ck[d] = 1;
-        } else {
-            e->blk_ck[d] = 2;
-            e->last_ck_blk_skipped++;
-        }
-    }
-    for (uint32_t d : cand)
-        if (e->blk_ck[d] == 1) e->blk_list.push_back(d);
-    if (e->blk_list.size() != cand.size()) {  // lay out the admitted ones alone
-        for (size_t q = 0; q < cand.size(); q++) {
-            e->cfg[cand[q]].map_off = keep_maps[q].first;
-            e->cfg[cand[q]].map_cap = keep_maps[q].second;
-        }
-        if ((rc = layout_hbm_docs(e, false, e->blk_list, keep_maps, total, mtot))) return rc;
-    }
-    return MTE_OK;
-}
-
-namespace {
-// e->order for the length of a pass that runs without its block documents: put back when the pass
-// ends, however it ends (d_order is uploaded again by the next pass)
-struct BlkGuard {
-    mte_engine* e;
-    std::vector<uint32_t> all;
-    std::vector<std::pair<uint64_t, uint32_t>> keep;  // the block documents' load-time (map_off, map_cap)
-    bool on = false;
-    ~BlkGuard() {
-        if (!on) return;
-        e->order.swap(all);
-        for (size_t q = 0; q < e->blk_list.size() && q < keep.size(); q++) {
-            e->cfg[e->blk_list[q]].map_off = keep[q].first;
-            e->cfg[e->blk_list[q]].map_cap = keep[q].second;
-        }
-    }
-};
-}  // namespace
 
 int run_kernel(mte_engine* e, bool gen) {
     HIP_TRY(e, hipSetDevice(e->device));
@@ -778,24 +437,8 @@ int run_kernel(mte_engine* e, bool gen) {
     }
     // a retained pass at level <= 1 runs its block documents on k_blk_ck; the rest of the pass is
     // routed as if they were not in the batch
-    uint64_t blk_bytes = 0, blk_maps = 0;
-    e->blk_list.clear();
-    e->blk_ck.clear();
-    e->map_blk_off.clear();
-    e->last_ck_blk_skipped = 0;
     BlkGuard og{e};
-    if (ck && !e->ext_needed) {
-        HIP_TRY(e, hipStreamSynchronize(e->stream));  // (layout_hbm_docs reads the uploaded op records)
-        if ((rc = blk_plan(e, og.keep, blk_bytes, blk_maps))) return rc;
-        if (!e->blk_list.empty()) {
-            og.all = e->order;
-            og.on = true;
-            e->order.erase(std::remove_if(e->order.begin(), e->order.end(), [&](uint32_t d) { return e->blk_ck[d] == 1; }),
-                           e->order.end());
-            e->d_order_stale = true;
-            if ((rc = upload(e, e->d_order, e->order))) return rc;
-        }
-    }
+    if ((rc = ck_blk_plan(e, ck && !e->ext_needed, og))) return rc;
     // nd: the documents this pass replays (e->order, LPT; a SharedMatrix batch's first pass runs
     // only its cell documents), nall: the batch's documents (results are indexed by document)
     const uint32_t nd = (uint32_t)e->order.size(), nall = e->P.n_docs;
@@ -828,23 +471,10 @@ int run_kernel(mte_engine* e, bool gen) {
     HIP_TRY(e, hipMemsetAsync(e->d_slot_bits.p, 0, e->d_slot_bits.n * sizeof(uint32_t), s_main));
     HIP_TRY(e, hipMemsetAsync(e->d_prof.p, 0, e->d_prof.n * sizeof(uint64_t), s_main));  // profiling build
     HIP_TRY(e, hipMemsetAsync(e->d_solo_started.p, 0, sizeof(uint32_t), s_main));  // k_solo_gate's counter
-    const uint32_t n_blk = (uint32_t)e->blk_list.size();
-    if (n_blk) {  // k_blk_ck's regions, map tables, list and counter
-        HIP_TRY(e, e->d_hbm_blk.fit(blk_bytes));
-        HIP_TRY(e, e->d_maps_blk.fit(std::max<uint64_t>(blk_maps, 1) * e->map_words));
-        HIP_TRY(e, e->d_blk_saved.fit(1));
-        e->map_blk_off.assign(nall, UINT64_MAX);
-        e->map_blk_cap.assign(nall, 0);
-        for (uint32_t d : e->blk_list) {
-            e->map_blk_off[d] = e->cfg[d].map_off;
-            e->map_blk_cap[d] = e->cfg[d].map_cap;
-        }
-        if ((rc = upload(e, e->d_blk_list, e->blk_list))) return rc;
-        HIP_TRY(e, hipMemsetAsync(e->d_blk_saved.p, 0, sizeof(uint32_t), s_main));
-    }
+    if ((rc = ck_blk_setup(e, og, s_main))) return rc;
     HIP_TRY(e, hipEventRecord(e->ev0, s_main));
     std::vector<uint32_t> spill;
-    e->map_rr_off.clear();  // (set again below for this pass's re-run documents)
+    e->maps_rr.clear();  // (set again below for this pass's re-run documents)
     float lds_ms = 0, hbm_ms = 0;
     // pass 1: the solo workgroups first (third stream: each takes a CU), then the LDS workgroups
     // (one per remaining CU, all of its LDS), then the HBM-resident waves on the second stream so
@@ -877,21 +507,8 @@ int run_kernel(mte_engine* e, bool gen) {
         HIP_TRY(e, hipEventRecord(e->ev2, s_hbmq));
         HIP_TRY(e, hipStreamWaitEvent(s_main, e->ev2, 0));
     }
-    // the block documents of a retained pass: k_blk_ck on the second stream beside the bulk, each in
-    // its own HBM region and map table (read back like the re-run documents', fetch_map_record),
-    // joined before emission
-    if (n_blk) {
-        HIP_TRY(e, hipStreamWaitEvent(s_hbmq, e->ev_gate, 0));  // (its list and counter went out before ev0)
-        Params pb = e->P;
-        pb.doc_list = e->d_blk_list.p;
-        pb.n_list = n_blk;
-        pb.hbm = e->d_hbm_blk.p;
-        pb.maps = e->d_maps_blk.p;
-        pb.map_rerun = 1;  // (worst-case tables: a full one is a capacity failure)
-        HIP_TRY(e, launch_blk_ck(pb, full, n_blk, e->d_blk_saved.p, s_hbmq));
-        HIP_TRY(e, hipEventRecord(e->ev_blk, s_hbmq));
-        HIP_TRY(e, hipStreamWaitEvent(s_main, e->ev_blk, 0));
-    }
+    // the block documents of a retained pass: k_blk_ck on the second stream beside the bulk
+    if ((rc = ck_blk_launch(e, full, s_hbmq, s_main))) return rc;
     const bool emit = !gen && e->emit_opt;
     e->emitted_legacy = e->legacy;
     e->emit_downloaded = false;
@@ -946,7 +563,6 @@ int run_kernel(mte_engine* e, bool gen) {
         e->last_resumed_docs = e->last_resumed_ops = e->last_resumed_docs_blk = e->last_ck_blk_saved = 0;
         e->last_resumed_ops_blk = 0;
     }
-    if (n_blk) HIP_TRY(e, hipMemcpy(&e->last_ck_blk_saved, e->d_blk_saved.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (ck && (rc = ck_end(e, ctr))) return rc;
     e->replayed = true;
     e->downloaded = false;
@@ -1046,16 +662,12 @@ int ensure_emit_download(mte_engine* e) {
 }
 
 // One property-map record of document d from the device: map_words words into w. The record is in
-// the re-run table when the host re-ran the document (rerun_spilled), else in the load-time one.
+// the re-run table when the host re-ran the document (rerun_spilled), else in k_blk_ck's when it was a
+// block document of a retained pass, else in the load-time one.
 int fetch_map_record(mte_engine* e, uint32_t d, uint32_t id, uint32_t* w) {
-    const bool rr = d < e->map_rr_off.size() && e->map_rr_off[d] != UINT64_MAX;
-    // (a block document of a retained pass: k_blk_ck's table)
-    const bool bk = !rr && d < e->map_blk_off.size() && e->map_blk_off[d] != UINT64_MAX;
-    if (id >= (rr ? e->map_rr_cap[d] : bk ? e->map_blk_cap[d] : e->cfg[d].map_cap))
-        return set_err(e, MTE_E_STATE, "catch-up: property map id out of range");
-    const uint32_t* base = rr   ? e->d_maps_rr.p + e->map_rr_off[d] * e->map_words
-                           : bk ? e->d_maps_blk.p + e->map_blk_off[d] * e->map_words
-                                : e->d_maps.p + e->cfg[d].map_off * e->map_words;
+    const MapSide* side = e->maps_rr.has(d) ? &e->maps_rr : e->maps_blk.has(d) ? &e->maps_blk : nullptr;
+    if (id >= (side ? side->cap[d] : e->cfg[d].map_cap)) return set_err(e, MTE_E_STATE, "catch-up: property map id out of range");
+    const uint32_t* base = side ? side->d.p + side->off[d] * e->map_words : e->d_maps.p + e->cfg[d].map_off * e->map_words;
     HIP_TRY(e, hipMemcpy(w, base + (uint64_t)id * e->map_words, e->map_words * 4, hipMemcpyDeviceToHost));
     return MTE_OK;
 }

@@ -24,6 +24,10 @@ def test_hip_free_units_and_rccl_include():
     for name in ("readback.cpp", "builder.cpp"):
         calls = HIP_CALL.findall(read(name))
         assert not calls, f"{name} calls the HIP API: {sorted(set(calls))}"
+    # the planning half of incremental replay stands without the engine object (tests/native/ck_plan_main.cpp)
+    calls = HIP_CALL.findall(read("ck_plan.hpp"))
+    assert not calls, f"ck_plan.hpp calls the HIP API: {sorted(set(calls))}"
+    assert not re.search(r"#\s*include\s*\"engine_host\.hpp\"", read("ck_plan.hpp"))
     sources = units() + sorted(
         os.path.basename(p) for ext in ("*.hpp", "*.h", "*.hip") for p in glob.glob(os.path.join(CSRC, ext))
     )
@@ -34,7 +38,7 @@ def test_hip_free_units_and_rccl_include():
 def test_makefile_links_every_unit():
     assert not os.path.exists(os.path.join(CSRC, "mte_host.cpp"))
     names = units()
-    assert {"engine_load.cpp", "engine_run.cpp", "readback.cpp", "gather.cpp", "diag.cpp", "builder.cpp"} <= set(names)
+    assert {"engine_load.cpp", "engine_run.cpp", "engine_ckpt.cpp", "readback.cpp", "gather.cpp", "diag.cpp", "builder.cpp"} <= set(names)
     makefile = read("Makefile").replace("\\\n", " ")
     m = re.search(r"^OBJS\s*:=\s*(.*)$", makefile, re.M)
     assert m, "the Makefile defines no OBJS"
