@@ -106,13 +106,45 @@ struct RgMark {
 enum RgStat : u32 {
     RS_OPS, RS_RESOLVE, RS_RES_ROWS, RS_RES_NROWS, RS_POP, RS_POP_BIG, RS_POP_HEAP, RS_FIND_ROWS, RS_SCOUR,
     RS_SCOUR_NOP, RS_SCOUR_SERIAL, RS_SCOUR_COPY, RS_PACK, RS_SPLIT_BLK, RS_MOVE_SLOTS, RS_SPLIT_AT,
-    RS_ZAM_CALLS, RS_ZAM_POPS, RS_LRU_PUSH, RS_RANGE_ROWS, RS_N
+    RS_ZAM_CALLS, RS_ZAM_POPS, RS_LRU_PUSH, RS_RANGE_ROWS, RS_DUO_HANDOVER, RS_DUO_SPEC_OK, RS_DUO_SPEC_REDO,
+    RS_DUO_NO_RESOLVE, RS_DUO_W_ROWS, RS_N
 };
 inline u64 g_rg_stats[RS_N + 64];
 #define RG_STAT(i, n) (g_rg_stats[i] += (u64)(n))
+// What a settle half running on a second wave would meet, counted on one wave: an op
+// whose settle pops the heap is a handover; W collects the rows its scours rewrote with other
+// contents (and every row from a pack's first row on); the next op's first resolve, done beside that
+// settle, would stand when W misses the rows it scanned and no pack ran, else it is repeated.
+struct RgDuoStat {
+    u64 w;
+    bool popped, packed, pending;
+    void settle_begin() {
+        if (pending) RG_STAT(RS_DUO_NO_RESOLVE, 1);  // (the op after the handover resolved nothing)
+        w = 0;
+        popped = packed = pending = false;
+    }
+    void settle_end() {
+        if (!popped) return;
+        RG_STAT(RS_DUO_HANDOVER, 1);
+        RG_STAT(RS_DUO_W_ROWS, __builtin_popcountll(w));
+        pending = true;
+    }
+    void resolved(bool ok, u32 row) {  // rows [0, row] scanned (every row when nothing was found)
+        if (!pending) return;
+        pending = false;
+        const u64 scanned = ok && row < 63 ? (2ull << row) - 1 : ~0ull;
+        if (packed || (w & scanned)) RG_STAT(RS_DUO_SPEC_REDO, 1);
+        else RG_STAT(RS_DUO_SPEC_OK, 1);
+    }
+};
+inline RgDuoStat g_rg_duo;
+#define RG_DUO(stmt) (g_rg_duo.stmt)
 #else
 #define RG_STAT(i, n) \
     do {              \
+    } while (0)
+#define RG_DUO(stmt) \
+    do {             \
     } while (0)
 #endif
 
@@ -513,9 +545,13 @@ struct RegEngine {
             carry = simd::readlane(incl, 63);
             if (++r >= nrows) break;
         }
-        if (!hit) return f;
+        if (!hit) {
+            RG_DUO(resolved(false, 0));
+            return f;
+        }
         if (inb) a = b;
         hit_row(a, r, hit, v, incl);
+        RG_DUO(resolved(true, f.row));
         return f;
     }
 
@@ -824,6 +860,7 @@ struct RegEngine {
         RG_COUNT(RP_N_POP, 1);
         const u32 n = heapSize, m = n - 1;
         RG_STAT(RS_POP, 1);
+        RG_DUO(popped = true);
         RG_STAT(RS_POP_BIG, m >= 128u);
         RG_STAT(RS_POP_HEAP, n);
 #if defined(MTE_CPU) && defined(MTE_CPU_STATS)
@@ -1054,6 +1091,7 @@ struct RegEngine {
         if constexpr (PROPS) cmp(w.props, 0u);
         if constexpr (WIDE) cmp(w.rm2, 0u);
         ns_put(w, k, SC_FALSE);  // scourNode's caller clears needsScour (mergeTree.ts:1457): same write
+        RG_DUO(w |= 1ull << r);
         rows.putrow(r, w);
         scoured = true;
         return nkeep;
@@ -1212,6 +1250,7 @@ struct RegEngine {
         if constexpr (PROPS) cmp(w.props, nullptr, 0u);
         if constexpr (WIDE) cmp(w.rm2, nullptr, 0u);
         ns_put(w, k, SC_FALSE);
+        RG_DUO(w |= 1ull << r);
         rows.putrow(r, w);
         scoured = true;
         return nkeep;
@@ -1244,6 +1283,7 @@ struct RegEngine {
         RG_PROF(RP_PACK);
         RG_COUNT(RP_N_PACK, 1);
         RG_STAT(RS_PACK, 1);
+        RG_DUO(packed = true);
         const u32 T = simd::readlane(simd::scan_incl(simd::sel(L() < m, cn, 0u)), 63);
         u32 kk = T / 4;
         if (kk > 7) kk = 7;
@@ -1566,9 +1606,26 @@ struct RegEngine {
                (n_lb < 57 || simd::readlane(LV.get(0), 56) == 0u);
     }
 
-    // Client.applyMsg for one op record (client.ts:805-836); false => not applied, hand off.
+    // Client.applyMsg for one op record (client.ts:805-836) in two halves, split where the op's own
+    // edit ends and the lazy clean-up begins:
+    //   apply_edit:   decode, checks, room, the insert / remove / annotate with its resolves, splits
+    //                 and needsScour marks (add_lru);
+    //   apply_settle: the two zamboni calls with the curSeq / minSeq advance between them.
+    // Nothing settle does changes what any (refSeq >= minSeq) view sees: scour drops tombstones at or
+    // below minSeq and merges settled text, pack redistributes slots; it changes only WHERE things are.
+    // apply() runs them back to back; every kernel and the CPU build replay through it.
     SD bool apply(const mte_op& op) {
         RG_PROF(RP_APPLY);
+        bool edited = false;
+        if (!apply_edit(op, edited)) return false;
+        if (status) return true;
+        RG_DUO(settle_begin());
+        apply_settle(op.seq, op.msn, (op.flags & MTE_F_END_OF_MSG) != 0, edited);
+        RG_DUO(settle_end());
+        return true;
+    }
+    // false => not applied, hand off; `edited`: the op changed the tree (the first zamboni runs)
+    SD bool apply_edit(const mte_op& op, bool& edited) {
         RG_STAT(RS_OPS, 1);
         const u32 type = op.type;
         const bool ins = type == MTE_OP_INSERT || type == MTE_OP_INSERT_MARKER;
@@ -1585,7 +1642,6 @@ struct RegEngine {
             fail(MTE_DOC_SEQ_ORDER, seq);
             return true;
         }
-        bool edited = false;
         if (ins) {
             RSeg rec;
             const bool mk = type == MTE_OP_INSERT_MARKER;
@@ -1610,26 +1666,29 @@ struct RegEngine {
             if constexpr (PROPS) edited = op_annotate(op.pos1, op.a, R, C, seq, op.props, (op.flags & MTE_F_REWRITE) != 0);
             count_op();
         }
-        if (status) return true;
+        return true;
+    }
+    // the settle half of an applied op (status 0 on entry): seq / msn of its record, eom its
+    // end-of-message flag
+    SD void apply_settle(i32 seq, i32 msn, bool eom, bool edited) {
         if (edited) {
             RG_PROF(RP_ZAM_EDIT);
             zamboni();
         }
-        if (status) return true;
-        if (op.flags & MTE_F_END_OF_MSG) {
+        if (status) return;
+        if (eom) {
             count_msg();
-            if (op.seq < curSeq || op.msn > op.seq || op.msn < minSeq) {
-                fail(MTE_DOC_SEQ_ORDER, op.seq);
-                return true;
+            if (seq < curSeq || msn > seq || msn < minSeq) {
+                fail(MTE_DOC_SEQ_ORDER, seq);
+                return;
             }
-            curSeq = op.seq;
-            if (op.msn > minSeq) {
+            curSeq = seq;
+            if (msn > minSeq) {
                 RG_PROF(RP_MSN);
-                minSeq = op.msn;
+                minSeq = msn;
                 zamboni();
             }
         }
-        return true;
     }
 
     // Replay ops [i, e): returns the first op not applied (e when done or failed; earlier when the

@@ -1,6 +1,7 @@
 """What the critical document's ops do, from the CPU build of the row engine with event statistics
 (tests/native MTE_CPU_STATS): per op, resolves and the rows they scan, heap pops and the heap size at
-a pop, scour outcomes, packs, block splits and slots moved. Sizes the device code paths (which path a
+a pop, scour outcomes, packs, block splits and slots moved, and what a settle half on a second wave
+would meet (handovers, first resolves that stand or are repeated). Sizes the device code paths (which path a
 pop takes, how many rows a resolve sees). Usage: python tools/rg_stats.py [ops] [gid]"""
 import ctypes
 import json
@@ -16,7 +17,7 @@ from tests import regcpu  # noqa: E402
 
 NAMES = ["ops", "resolve", "res_rows", "res_nrows", "pop", "pop_big", "pop_heap", "find_rows", "scour", "scour_nop",
          "scour_serial", "scour_copy", "pack", "split_blk", "move_slots", "split_at", "zam_calls", "zam_pops", "lru_push",
-         "range_rows"]
+         "range_rows", "duo_handover", "duo_spec_ok", "duo_spec_redo", "duo_no_resolve", "duo_w_rows"]
 
 
 def main():
@@ -48,6 +49,10 @@ def main():
         "heap_at_pop": round(st["pop_heap"] / max(st["pop"], 1), 1),
         "pops_on_serial_sift": round(st["pop_big"] / max(st["pop"], 1), 4),
         "slots_moved_per_split": round(st["move_slots"] / max(st["split_blk"] + st["pack"], 1), 1),
+        # a settle half on a second wave: of the ops after one whose settle pops, the
+        # share whose first resolve would have to be repeated, and the rows a popping settle rewrites
+        "duo_redo_share": round(st["duo_spec_redo"] / max(st["duo_spec_ok"] + st["duo_spec_redo"], 1), 4),
+        "duo_rows_rewritten_per_handover": round(st["duo_w_rows"] / max(st["duo_handover"], 1), 3),
         "heap_max_at_pop": heap_max,
         "n_lb_max_at_pop": lb_max,
     }
