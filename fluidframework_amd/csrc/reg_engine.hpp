@@ -107,7 +107,11 @@ enum RgStat : u32 {
     RS_OPS, RS_RESOLVE, RS_RES_ROWS, RS_RES_NROWS, RS_POP, RS_POP_BIG, RS_POP_HEAP, RS_FIND_ROWS, RS_SCOUR,
     RS_SCOUR_NOP, RS_SCOUR_SERIAL, RS_SCOUR_COPY, RS_PACK, RS_SPLIT_BLK, RS_MOVE_SLOTS, RS_SPLIT_AT,
     RS_ZAM_CALLS, RS_ZAM_POPS, RS_LRU_PUSH, RS_RANGE_ROWS, RS_DUO_HANDOVER, RS_DUO_SPEC_OK, RS_DUO_SPEC_REDO,
-    RS_DUO_NO_RESOLVE, RS_DUO_W_ROWS, RS_N
+    RS_DUO_NO_RESOLVE, RS_DUO_W_ROWS,
+    // removes (op_remove): all; p2's block in p1's row; of those, neither split split its block; the
+    // rows second resolves scan (RS_RANGE_ROWS: the rows marking passes scan). Pack's sibling pass: its
+    // scour calls and the ones among them that left their block as it was.
+    RS_REM, RS_REM_SAMEROW, RS_REM_SAMEROW_NOSPLIT, RS_RES2_ROWS, RS_PACK_SCOUR, RS_PACK_SCOUR_NOP, RS_N
 };
 inline u64 g_rg_stats[RS_N + 64];
 #define RG_STAT(i, n) (g_rg_stats[i] += (u64)(n))
@@ -833,14 +837,27 @@ struct RegEngine {
         u32 k = 1;
         u64 path = 0;  // nodes of register 0 that take their child's entry
         // G bit k: node k takes its chosen child's entry (the moved entry goes below k); Rt bit k:
-        // that child is the right one. The path from the root follows them in scalar registers
-        // (one crossbar round trip fewer than gathering each child's parent decision); nodes
-        // 32..63 continue into register 1.
+        // that child is the right one. The path from the root follows them (one crossbar round trip
+        // fewer than gathering each child's parent decision); nodes 32..63 continue into register 1.
         const u64 G = simd::ballot(go), Rt = simd::ballot(right);
-        while (k < 64u) {
-            if (!((G >> k) & 1u)) break;
-            path |= 1ull << k;
-            k = 2 * k + (u32)((Rt >> k) & 1u);
+        // Every lane decides for itself whether the walk reaches it, in straight-line code: E bit l
+        // says node l is its parent's chosen child and the parent lets the entry pass (the root and
+        // lane 0's bit are set), and the walk reaches l iff E holds for l and for each of its at most
+        // five ancestors l >> j (all below 32; a shift that runs out reads bit 0 or 1, both set).
+        const V Lv = L();
+        const V pa = Lv >> 1u;
+        const V ec = (simd::splat((u32)G) >> pa) & (((simd::splat((u32)Rt) >> pa) ^ Lv) ^ 0xFFFFFFFFu);
+        const B e = ((ec & 1u) != 0u) | (Lv < 2u);
+        const V Es = simd::splat((u32)simd::ballot(e) | 3u);
+        const V anc = (Es >> pa) & (Es >> (Lv >> 2u)) & (Es >> (Lv >> 3u)) & (Es >> (Lv >> 4u)) & (Es >> (Lv >> 5u));
+        const u64 reach = simd::ballot(e & ((anc & 1u) != 0u)) & ~1ull;
+        path = reach & G;
+        const u64 stop = reach & ~G;  // the node the walk ends at, when it ends in register 0
+        if (stop) {
+            k = (u32)__builtin_ctzll(stop);
+        } else {  // through a node of the last level of register 0 into register 1
+            const u32 n5 = 63u - (u32)__builtin_clzll(path);
+            k = 2 * n5 + (u32)((Rt >> n5) & 1u);
         }
         const B mv = simd::ballot_mask(path);
         V N0 = simd::sel(mv, kc, K0), T0 = simd::sel(mv, sc, S0);
@@ -857,6 +874,12 @@ struct RegEngine {
     }
     SD u32 heap_pop() {
         RG_PROF(RP_HEAP);
+        const u32 top = hrd<0>(HS, 1);
+        heap_pop_rest();
+        return top;
+    }
+    // everything of a pop but reading the root's segment id
+    SD void heap_pop_rest() {
         RG_COUNT(RP_N_POP, 1);
         const u32 n = heapSize, m = n - 1;
         RG_STAT(RS_POP, 1);
@@ -867,7 +890,6 @@ struct RegEngine {
         if (n > g_rg_stats[RS_N]) g_rg_stats[RS_N] = n;  // the largest heap at a pop
         if (n_lb > g_rg_stats[RS_N + 1]) g_rg_stats[RS_N + 1] = n_lb;
 #endif
-        const u32 top = hrd<0>(HS, 1);
         const u32 lk = hkey(n), ls = hsid(n);
         i32 newTop = (i32)lk;
         if (m >= 1) {
@@ -876,7 +898,32 @@ struct RegEngine {
         }
         heapTop = newTop;
         heapSize = m;
-        return top;
+    }
+    // zamboni's pop: the popped segment's leaf block (find_seg) with it. The segment id is the heap's
+    // root, known before the sift, and the search reads nothing the sift writes: the first eight
+    // rows' ids are read first and arrive while the sift runs -- one LDS round trip of latency per pop
+    // where heap_pop() + find_seg() wait for two. (LDS returns in order: the counter waits of the
+    // sift's crossbar gathers cover these reads.)
+    SD u32 heap_pop_find() {
+        const u32 sid = hrd<0>(HS, 1);
+        const u32 nrows = (n_lb + 7) >> 3;
+        V s8[8];
+        for (u32 i = 0; i < 8; i++) s8[i] = ld_sid(i < nrows ? i : 0u);
+        simd::issue_here();
+        {
+            RG_PROF(RP_HEAP);
+            heap_pop_rest();
+        }
+        RG_PROF(RP_FIND_SEG);
+        RG_STAT(RS_FIND_ROWS, nrows);
+        V hr = simd::splat(NONE);
+        for (u32 i = 8; i-- > 0;) hr = simd::sel(s8[i] == sid, i, hr);  // rows past nrows re-read row 0: i = 0 wins
+        const u64 m = simd::ballot(hr != NONE);
+        if (m) {
+            const u32 l = (u32)__builtin_ctzll(m);
+            return simd::readlane(hr, l) * 8 + (l >> 3);
+        }
+        return nrows > 8 ? find_seg(sid, 8) : NONE;
     }
     // addToLRUSet (mergeTree.ts:1273-1283) for a segment of block k
     SD void add_lru(u32 k, u32 sid, i32 seq) {
@@ -889,11 +936,11 @@ struct RegEngine {
     // the leaf block holding segment sid (segment.parent), NONE when unlinked. Segment ids are
     // unique, so each batch of eight rows needs one per-lane select per row and ONE ballot (no
     // branch per row): the hit lane's row index comes back with one readlane.
-    SD u32 find_seg(u32 sid) {
+    SD u32 find_seg(u32 sid, u32 from = 0) {  // from: the first row to look at (a multiple of 8)
         RG_PROF(RP_FIND_SEG);
         const u32 nrows = (n_lb + 7) >> 3;
-        RG_STAT(RS_FIND_ROWS, nrows);
-        for (u32 r0 = 0; r0 < nrows; r0 += 8) {  // eight rows' reads in flight per round
+        if (!from) RG_STAT(RS_FIND_ROWS, nrows);
+        for (u32 r0 = from; r0 < nrows; r0 += 8) {  // eight rows' reads in flight per round
             V s8[8];
             for (u32 i = 0; i < 8; i++) s8[i] = ld_sid(r0 + i < nrows ? r0 + i : r0);
             V hr = simd::splat(NONE);
@@ -1389,8 +1436,7 @@ struct RegEngine {
         for (int i = 0; i < 2 && !status; i++) {
             if (heapSize == 0 || heapTop > minSeq) break;
             RG_STAT(RS_ZAM_POPS, 1);
-            const u32 sid = heap_pop();
-            const u32 k = find_seg(sid);
+            const u32 k = heap_pop_find();
             if (k == NONE) continue;  // no longer linked
             if (ns_get(k) == SC_FALSE) continue;
             const u32 cnt = count(k);
@@ -1407,8 +1453,10 @@ struct RegEngine {
             }
             V cn = simd::splat(0);
             for (u32 idx = 0; idx < m; idx++) {
+                RG_STAT(RS_PACK_SCOUR, 1);
                 const u32 c = scour(k0 + idx, count(k0 + idx));
                 if (status) return;
+                if (!scoured) RG_STAT(RS_PACK_SCOUR_NOP, 1);
                 cn = simd::writelane(cn, idx, c);
             }
             pack_leaves(pi, m, k0, cn);
@@ -1490,13 +1538,23 @@ struct RegEngine {
         // the p2 resolve and the marking start at p1's row: nothing before it moves or changes
         // visible length (a split keeps the lengths, a block split shifts only later blocks)
         u32 r1 = 0, c1 = 0;
+        RG_STAT(RS_REM, 1);
+        [[maybe_unused]] bool f1ok = false, bsplit = false;  // (statistics only)
         for (u32 ph = 0; ph < 2; ph++) {
             const RFound f = resolve(ph ? p2 : p1, R, C, r1, c1);
             if (ph == 0 && f.ok) {
                 r1 = f.row;
                 c1 = f.carry;
+                f1ok = true;
             }
-            if (!f.ok || !(f.slot >= 0 && f.r > 0)) continue;
+            const bool split = f.ok && f.slot >= 0 && f.r > 0;
+            bsplit = bsplit || (split && f.cnt + 1 >= 8);
+            if (ph) {
+                RG_STAT(RS_RES2_ROWS, f.ok ? f.row - r1 + 1 : ((n_lb + 7) >> 3) - r1);
+                RG_STAT(RS_REM_SAMEROW, f1ok && f.ok && f.row == r1);
+                RG_STAT(RS_REM_SAMEROW_NOSPLIT, f1ok && f.ok && f.row == r1 && !bsplit);
+            }
+            if (!split) continue;
             if (split_at(f) == NONE || status) return false;
         }
         RG_PROF(RP_RANGE);
@@ -1504,6 +1562,7 @@ struct RegEngine {
         u32 carry = c1;
         const u32 cbit = WIDE ? 1u << (C & 31u) : 1u << C;
         for (u32 r = r1; r < nrows && (i32)carry < p2; r++) {
+            RG_STAT(RS_RANGE_ROWS, 1);
             Row& w = rows.rowref(r);
             const V v = vis(w, R, C);
             const V incl = simd::scan_incl(v) + carry;

@@ -71,6 +71,7 @@ SD V operator&(V a, V b) { return {a.x & b.x}; }
 SD V operator&(V a, u32 b) { return {a.x & b}; }
 SD V operator|(V a, V b) { return {a.x | b.x}; }
 SD V operator|(V a, u32 b) { return {a.x | b}; }
+SD V operator^(V a, V b) { return {a.x ^ b.x}; }
 SD V operator^(V a, u32 b) { return {a.x ^ b}; }
 SD V operator*(V a, u32 b) { return {a.x * b}; }
 SD V operator<<(V a, u32 s) { return {a.x << s}; }
@@ -208,6 +209,9 @@ SD void count_add(u32* ctr, u32 n) { atomicAdd(ctr, n); }
 SD void wait_loaded(V v) { asm volatile("" ::"v"(v.x)); }
 // keep_branch: the conditional block this stands in stays a branch (is not turned into selects).
 SD void keep_branch() { asm volatile(""); }
+// issue_here: the instructions before this point are issued before the ones after it (loads that are
+// to run under the work that follows).
+SD void issue_here() { __builtin_amdgcn_sched_barrier(0); }
 
 #else
 // ---------------------------------------------------------------------------------- CPU backend
@@ -406,6 +410,7 @@ SD T reserve(T* ctr, T n) {
 SD void count_add(u32* ctr, u32 n) { *ctr += n; }
 SD void wait_loaded(V) {}
 SD void keep_branch() {}
+SD void issue_here() {}
 #undef MTE_L
 #endif
 

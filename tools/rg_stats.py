@@ -17,7 +17,11 @@ from tests import regcpu  # noqa: E402
 
 NAMES = ["ops", "resolve", "res_rows", "res_nrows", "pop", "pop_big", "pop_heap", "find_rows", "scour", "scour_nop",
          "scour_serial", "scour_copy", "pack", "split_blk", "move_slots", "split_at", "zam_calls", "zam_pops", "lru_push",
-         "range_rows", "duo_handover", "duo_spec_ok", "duo_spec_redo", "duo_no_resolve", "duo_w_rows"]
+         "range_rows", "duo_handover", "duo_spec_ok", "duo_spec_redo", "duo_no_resolve", "duo_w_rows",
+         # removes: all; p2's block in p1's row; of those with no block split in the remove; rows the second
+         # resolves scan (range_rows: rows the marking passes scan); pack's sibling pass: its scour calls and
+         # the ones among them that left their block as it was
+         "rem", "rem_same_row", "rem_same_row_no_blk_split", "res2_rows", "pack_scour", "pack_scour_nop"]
 
 
 def main():
@@ -49,6 +53,10 @@ def main():
         "heap_at_pop": round(st["pop_heap"] / max(st["pop"], 1), 1),
         "pops_on_serial_sift": round(st["pop_big"] / max(st["pop"], 1), 4),
         "slots_moved_per_split": round(st["move_slots"] / max(st["split_blk"] + st["pack"], 1), 1),
+        "removes_same_row_share": round(st["rem_same_row"] / max(st["rem"], 1), 4),
+        "removes_same_row_no_blk_split_share": round(st["rem_same_row_no_blk_split"] / max(st["rem"], 1), 4),
+        "find_rows_per_pop": round(st["find_rows"] / max(st["pop"], 1), 3),
+        "pack_scours_per_pack": round(st["pack_scour"] / max(st["pack"], 1), 3),
         # a settle half on a second wave: of the ops after one whose settle pops, the
         # share whose first resolve would have to be repeated, and the rows a popping settle rewrites
         "duo_redo_share": round(st["duo_spec_redo"] / max(st["duo_spec_ok"] + st["duo_spec_redo"], 1), 4),
