@@ -9,6 +9,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <string>
 #include <thread>
@@ -80,20 +81,54 @@ static int derive_value_tables(mte_engine* e) {
     e->val_flags.assign(nv, 0);
     e->val_objidx.assign(nv, NONE);
     e->val_objmatch.assign(nv, 0);
-    std::vector<uint32_t> objs;
+    // val_match(a, b) is a == b, or bit val_objidx[b] of val_objmatch[a]: a column only for an object
+    // value that some OTHER value id equals (the same object in another key order, an array and its
+    // index object, ...). Every other object value matches its own id alone, and a == b covers that.
+    // A stored value is never null (id 0, a delete), so b is truthy, and matchProperties(a, b) then
+    // needs a truthy with the same for-in keys: only values with equal key sets are compared.
+    typedef std::vector<std::u16string> KeySet;
+    auto key_set = [&](uint32_t v) {
+        KeySet k = json::for_in(&vals[v]);
+        std::sort(k.begin(), k.end());
+        return k;
+    };
+    std::map<KeySet, std::vector<uint32_t>> groups;  // key set of some object value -> values with it
+    std::vector<uint8_t> sizes;                      // sizes[n]: some object value has n keys
     for (uint32_t v = 0; v < nv; v++) {
         if (!json::truthy(&vals[v])) e->val_flags[v] |= 1u;
         if (json::is_object_typed(&vals[v]) && v != 0) {
             e->val_flags[v] |= 2u;
-            if (objs.size() < 64) {
-                e->val_objidx[v] = (uint32_t)objs.size();
-                objs.push_back(v);
-            }
+            KeySet k = key_set(v);
+            if (sizes.size() <= k.size()) sizes.resize(k.size() + 1, 0);
+            sizes[k.size()] = 1;
+            groups[std::move(k)];
         }
     }
-    for (uint32_t v = 0; v < nv; v++)
-        for (size_t j = 0; j < objs.size(); j++)
-            if (json::match_properties(&vals[v], &vals[objs[j]])) e->val_objmatch[v] |= 1ull << j;
+    for (uint32_t v = 1; v < nv && !groups.empty(); v++) {
+        if (e->val_flags[v] & 1u) continue;
+        // (a string's for-in keys are its indices: skip one no object value's key count equals)
+        const size_t n = vals[v].kind == json::Value::String ? vals[v].str.size() : 0;
+        if (vals[v].kind == json::Value::String && (n >= sizes.size() || !sizes[n])) continue;
+        auto it = groups.find(key_set(v));
+        if (it != groups.end()) it->second.push_back(v);
+    }
+    uint32_t n_cols = 0;
+    for (auto& g : groups)
+        for (uint32_t b : g.second) {
+            if (!(e->val_flags[b] & 2u)) continue;
+            for (uint32_t a : g.second) {
+                if (a == b || !json::match_properties(&vals[a], &vals[b])) continue;
+                if (e->val_objidx[b] == NONE) {
+                    if (n_cols == 64)
+                        return set_err(e, MTE_E_UNSUPPORTED,
+                                       "more than 64 object values of the batch's properties equal another value "
+                                       "(matchProperties): the match table has 64 columns");
+                    e->val_objidx[b] = n_cols++;
+                    e->val_objmatch[b] |= 1ull << e->val_objidx[b];
+                }
+                e->val_objmatch[a] |= 1ull << e->val_objidx[b];
+            }
+        }
     uint32_t nk = (uint32_t)hb.key_offsets.size() - 1;
     e->key_is_index.assign(nk, 0);
     e->key_index.assign(nk, 0);

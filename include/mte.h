@@ -255,7 +255,9 @@ int mte_create(const mte_config* cfg, mte_engine** out);
 void mte_destroy(mte_engine* e);
 const char* mte_last_error(const mte_engine* e);
 
-/* Stage a batch on the device (copies host buffers; returns after the upload). */
+/* Stage a batch on the device (copies host buffers; returns after the upload).
+ * MTE_E_UNSUPPORTED when more than 64 object-typed property values of the batch each equal another
+ * value of it under matchProperties (properties.ts:62-93; e.g. one object in two key orders). */
 int mte_load(mte_engine* e, const mte_batch* batch);
 
 /* Client.applyMsg for every message of every document (client.ts:805-836), on the GPU.
