@@ -58,7 +58,9 @@ constexpr u32 NS_SHIFT = 24, NS_MASK = 3u << NS_SHIFT;
 enum RgProf : u32 {
     RP_TOTAL, RP_FETCH, RP_APPLY, RP_RESOLVE, RP_INSERT_SLOT, RP_SPLIT, RP_RANGE, RP_ZAMBONI, RP_SCOUR,
     RP_HEAP, RP_FIND_SEG, RP_PACK, RP_LRU, RP_OPS, RP_N_RESOLVE, RP_N_SCOUR, RP_N_SCOUR_CHANGED,
-    RP_N_PACK, RP_N_POP, RP_N_SPLIT_BLK, RP_N_MOVE, RP_SPLIT_AT, RP_INS, RP_REM, RP_MSN, RP_ZAM_EDIT, RP_N
+    RP_N_PACK, RP_N_POP, RP_N_SPLIT_BLK, RP_N_MOVE, RP_SPLIT_AT, RP_INS, RP_REM, RP_MSN, RP_ZAM_EDIT,
+    RP_PACK_SIBS,  // pack's sibling pass (zamboni's loop of scours in front of pack_leaves); reported as "scour_chain"
+    RP_N
 };
 #if defined(MTE_PROFILE) && !defined(MTE_CPU)
 // RG_PROF_ONLY=<slot>: time that one scope only (each s_memtime pair costs a lone wave ~100 cycles,
@@ -111,7 +113,17 @@ enum RgStat : u32 {
     // removes (op_remove): all; p2's block in p1's row; of those, neither split split its block; the
     // rows second resolves scan (RS_RANGE_ROWS: the rows marking passes scan). Pack's sibling pass: its
     // scour calls and the ones among them that left their block as it was.
-    RS_REM, RS_REM_SAMEROW, RS_REM_SAMEROW_NOSPLIT, RS_RES2_ROWS, RS_PACK_SCOUR, RS_PACK_SCOUR_NOP, RS_N
+    RS_REM, RS_REM_SAMEROW, RS_REM_SAMEROW_NOSPLIT, RS_RES2_ROWS, RS_PACK_SCOUR, RS_PACK_SCOUR_NOP,
+    // The shape of a pack (profiles/r10/pack_stats.json): the times the sibling pass's second scour of
+    // the popped block changed it (not a no-op: it cannot be skipped); the other siblings the pass
+    // changed; packs whose siblings lie in one row / in two; with a sibling on the serial
+    // walk; with an arena_gc during the pass; that cascade into pack_internal; with 8 siblings; that
+    // end with more blocks than siblings; the sums of siblings (m) and of resulting blocks (kk).
+    RS_PACK_SELF_CHANGED, RS_PACK_SIB_CHANGED, RS_PACK_ONE_ROW, RS_PACK_TWO_ROWS, RS_PACK_SERIAL, RS_PACK_GC,
+    RS_PACK_CASCADE, RS_PACK_M8, RS_PACK_GROWS, RS_PACK_M_SUM, RS_PACK_KK_SUM,
+    // needsScour marks (add_lru): written as a second write of the row the edit has just written, and
+    // folded into the edit's own row write
+    RS_LRU_REWRITE, RS_LRU_FOLDED, RS_N
 };
 inline u64 g_rg_stats[RS_N + 64];
 #define RG_STAT(i, n) (g_rg_stats[i] += (u64)(n))
@@ -184,6 +196,12 @@ struct RFound {
 template <int NR = (int)RG_ROWS, bool PAGED = false, bool PROPS = false, bool WIDE = false>
 struct RegEngine {
     static constexpr bool kProps = PROPS, kWide = WIDE;
+    // An edit's needsScour marks go into the row write the edit makes anyway (insert_slot, op_remove) on
+    // the engines that own a whole row store: k_solo's and k_rows_cont's. On k_rows (a quarter's fixed
+    // rows, the paged pool) the same code measured slower -- C3 +7 %, C5 +1.4 %, C2 +1-3 %, the 12-wave
+    // builds spilling 19-25 VGPRs more at their 168-register bound -- and they keep add_lru's second
+    // write of the row.
+    static constexpr bool kFoldLru = !PAGED && NR == (int)RG_ROWS;
     static constexpr u32 MAXC = WIDE ? 64u : 32u;  // client ids below this (rm, rm2)
     typedef simd::V V;
     typedef simd::B B;
@@ -453,6 +471,10 @@ struct RegEngine {
     SD static B in_group(u32 k) { return (L() >> 3) == (k & 7u); }
     SD static u32 group_bits(u64 m, u32 k) { return (u32)((m >> gbase(k)) & 0xFFull); }
     SD static u32 count_in(const Row& w, u32 k) { return (u32)__builtin_popcount(group_bits(simd::ballot(w.len != 0u), k)); }
+    // Every lane of a block's group holds the block's needsScour, empty slots included: ns_put writes
+    // the whole group, insert_slot gives the new slot its block's bits, split_block, scour's compaction
+    // and pack_leaves keep or clear them group-wide. ns_in reads the first lane; op_remove's marking
+    // loop reads the lanes it marks.
     SD static u32 ns_in(const Row& w, u32 k) { return (simd::readlane(w.meta, gbase(k)) >> NS_SHIFT) & 3u; }
     SD static void ns_put(Row& w, u32 k, u32 sc) { w.meta = simd::sel(in_group(k), (w.meta & ~NS_MASK) | (sc << NS_SHIFT), w.meta); }
     SD u32 count(u32 k) { return count_in(rows.row(k >> 3), k); }
@@ -617,8 +639,13 @@ struct RegEngine {
     // Insert `rec` at slot j of block k (child count cnt); a block reaching 8 children splits 4+4,
     // the new block right after it in document order (needsScour undefined). With `upd`, slot j-1
     // first takes (len ul, cap uc) (the left piece of a split). Returns the block holding rec.
-    SD u32 insert_slot(u32 k, u32 cnt, u32 j, const RSeg& rec, bool upd, u32 ul, u32 uc) {
+    // `lru`: the seq addToLRUSet is due with for rec (0: none). With kFoldLru, where the block does not
+    // split, the needsScour mark goes into this row write and the heap push follows it (lruFolded: add_lru is
+    // done); a splitting block leaves it to the caller's add_lru on the block rec ends up in.
+    bool lruFolded = false;
+    SD u32 insert_slot(u32 k, u32 cnt, u32 j, const RSeg& rec, bool upd, u32 ul, u32 uc, i32 lru = 0) {
         RG_PROF(RP_INSERT_SLOT);
+        lruFolded = false;
         if (cnt >= 8 || j > cnt) {
             fail(MTE_DOC_CAPACITY, curSeq);
             return NONE;
@@ -629,7 +656,18 @@ struct RegEngine {
         const B ing = in_group(k);
         const B mv = ing & (sl > j);
         const B at = L() == gb + j;
-        const u32 ns = (simd::readlane(w.meta, gb) >> NS_SHIFT) & 3u;
+        u32 ns = (simd::readlane(w.meta, gb) >> NS_SHIFT) & 3u;
+        bool push = false;
+        if constexpr (kFoldLru) {
+            if (lru && cnt + 1 < 8) {
+                lruFolded = true;
+                if (ns != SC_TRUE && lru > curSeq) {
+                    push = true;
+                    ns = SC_TRUE;
+                    ns_put(w, k, SC_TRUE);
+                }
+            }
+        }
         if (upd) {
             const B lf = L() == gb + j - 1;
             w.len = simd::sel(lf, ul, w.len);
@@ -650,6 +688,10 @@ struct RegEngine {
         if constexpr (PROPS) put(w.props, rec.props);
         if constexpr (WIDE) put(w.rm2, rec.rm2);
         rows.writeback(r);
+        if (push) {
+            RG_STAT(RS_LRU_FOLDED, 1);
+            heap_push(rec.sid, lru);
+        }
         if (cnt + 1 < 8) return k;
         split_block(k);
         return j < 4 ? k : k + 1;
@@ -929,6 +971,7 @@ struct RegEngine {
     SD void add_lru(u32 k, u32 sid, i32 seq) {
         RG_PROF(RP_LRU);
         if (ns_get(k) != SC_TRUE && seq > curSeq) {
+            RG_STAT(RS_LRU_REWRITE, 1);
             ns_set(k, SC_TRUE);
             heap_push(sid, seq);
         }
@@ -1336,6 +1379,9 @@ struct RegEngine {
         if (kk > 7) kk = 7;
         if (kk < 1) kk = 1;
         const u32 base = T / kk, extra = T % kk;
+        RG_STAT(RS_PACK_KK_SUM, kk);
+        RG_STAT(RS_PACK_GROWS, kk > m);
+        RG_STAT(RS_PACK_CASCADE, kk < 4 && height > 2);
         if (!ensure_blocks(n_lb + kk - m)) return;
         // item t (lane t < T) of the concatenated children: block k0 + sib, slot q
         V sib = simd::splat(0), q = L();
@@ -1452,13 +1498,31 @@ struct RegEngine {
                 return;
             }
             V cn = simd::splat(0);
-            for (u32 idx = 0; idx < m; idx++) {
-                RG_STAT(RS_PACK_SCOUR, 1);
-                const u32 c = scour(k0 + idx, count(k0 + idx));
-                if (status) return;
-                if (!scoured) RG_STAT(RS_PACK_SCOUR_NOP, 1);
-                cn = simd::writelane(cn, idx, c);
+#if defined(MTE_CPU) && defined(MTE_CPU_STATS)
+            const u64 serial0 = g_rg_stats[RS_SCOUR_SERIAL];
+            const u32 gc0 = n_gc;
+            RG_STAT(((k0 + m - 1) >> 3) == (k0 >> 3) ? RS_PACK_ONE_ROW : RS_PACK_TWO_ROWS, 1);
+            RG_STAT(RS_PACK_M8, m == 8);
+            RG_STAT(RS_PACK_M_SUM, m);
+#endif
+            // The popped block k is among them and is scoured a second time, as scourNode is in the
+            // reference: a tombstone the first pass dropped had reset the merge chain, and the settled
+            // text on its two sides, adjacent now, joins in this pass (RS_PACK_SELF_CHANGED counts it).
+            {
+                RG_PROF(RP_PACK_SIBS);
+                for (u32 idx = 0; idx < m; idx++) {
+                    RG_STAT(RS_PACK_SCOUR, 1);
+                    const u32 c = scour(k0 + idx, count(k0 + idx));
+                    if (status) return;
+                    if (!scoured) RG_STAT(RS_PACK_SCOUR_NOP, 1);
+                    else RG_STAT(k0 + idx == k ? RS_PACK_SELF_CHANGED : RS_PACK_SIB_CHANGED, 1);
+                    cn = simd::writelane(cn, idx, c);
+                }
             }
+#if defined(MTE_CPU) && defined(MTE_CPU_STATS)
+            RG_STAT(RS_PACK_SERIAL, g_rg_stats[RS_SCOUR_SERIAL] != serial0);
+            RG_STAT(RS_PACK_GC, n_gc != gc0);
+#endif
             pack_leaves(pi, m, k0, cn);
         }
     }
@@ -1525,9 +1589,9 @@ struct RegEngine {
         if (rec.len == 0) return false;  // blockInsert skips empty segments (:2196)
         rec.sid = new_sid();
         if (rec.sid == NONE) return false;
-        const u32 b = insert_slot(k, f.cnt, j, rec, false, 0, 0);
+        const u32 b = insert_slot(k, f.cnt, j, rec, false, 0, 0, seq > minSeq ? seq : 0);
         if (status) return false;
-        if (seq > minSeq) add_lru(b, rec.sid, seq);
+        if (seq > minSeq && !lruFolded) add_lru(b, rec.sid, seq);
         return status == 0;
     }
 
@@ -1580,14 +1644,38 @@ struct RegEngine {
             }
             w.meta = simd::sel(was, w.meta | F_OVL, simd::sel(fresh, (w.meta & ~0xFF00u) | (C << 8) | F_REMOVED, w.meta));
             w.rseq = simd::sel(fresh, (u32)seq, w.rseq);
-            rows.writeback(r);
-            // addToLRUSet per block, document order: the first marked slot of each block
-            for (u64 gm = mm; gm;) {
-                const u32 l = (u32)__builtin_ctzll(gm);
-                const u32 g = l >> 3;
-                gm &= ~(0xFFull << (g * 8));
-                add_lru(r * 8 + g, simd::readlane(w.sid, l), seq);
-                if (status) return false;
+            if constexpr (kFoldLru) {
+                // addToLRUSet per block, document order, at the first marked slot of each block: the
+                // needsScour marks go into this row write, the heap pushes follow it
+                u64 pm = 0;
+                if (seq > curSeq) {
+                    const u64 nst = simd::ballot(((w.meta >> NS_SHIFT) & 3u) == SC_TRUE);  // (every lane of a block holds it)
+                    u64 grp = 0;
+                    for (u64 gm = mm & ~nst; gm;) {
+                        const u32 l = (u32)__builtin_ctzll(gm);
+                        const u64 g8 = 0xFFull << (l & ~7u);
+                        gm &= ~g8;
+                        pm |= 1ull << l;
+                        grp |= g8;
+                    }
+                    if (grp) w.meta = simd::sel(simd::ballot_mask(grp), (w.meta & ~NS_MASK) | (SC_TRUE << NS_SHIFT), w.meta);
+                }
+                rows.writeback(r);
+                for (; pm; pm &= pm - 1) {
+                    RG_STAT(RS_LRU_FOLDED, 1);
+                    heap_push(simd::readlane(w.sid, (u32)__builtin_ctzll(pm)), seq);
+                    if (status) return false;
+                }
+            } else {
+                rows.writeback(r);
+                // addToLRUSet per block, document order: the first marked slot of each block
+                for (u64 gm = mm; gm;) {
+                    const u32 l = (u32)__builtin_ctzll(gm);
+                    const u32 g = l >> 3;
+                    gm &= ~(0xFFull << (g * 8));
+                    add_lru(r * 8 + g, simd::readlane(w.sid, l), seq);
+                    if (status) return false;
+                }
             }
         }
         return status == 0;
@@ -1936,7 +2024,7 @@ struct RegEngine {
                                               PF_RANGE, PF_ZAMBONI, PF_SCOUR, PF_HEAP, PF_FIND_SEG, PF_PACK,
                                               PF_LRU, PF_OPS, PN_RESOLVE, PN_SCOUR, PN_SCOUR_CHANGED, PN_PACK,
                                               PN_POP, PN_SPLIT_BLK, PN_DIRTY, PF_ALLOC, PF_OP_INS, PF_OP_REM,
-                                              PF_ZAM_MSN, PF_ZAM_EDIT};
+                                              PF_ZAM_MSN, PF_ZAM_EDIT, PF_SCOUR_CHAIN};
             u64* o2 = p.prof + (u64)doc * PROF_SLOTS;
             for (u32 i = 0; i < RP_N; i++) o2[map[i]] += pf[i];
         }

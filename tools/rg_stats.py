@@ -21,7 +21,16 @@ NAMES = ["ops", "resolve", "res_rows", "res_nrows", "pop", "pop_big", "pop_heap"
          # removes: all; p2's block in p1's row; of those with no block split in the remove; rows the second
          # resolves scan (range_rows: rows the marking passes scan); pack's sibling pass: its scour calls and
          # the ones among them that left their block as it was
-         "rem", "rem_same_row", "rem_same_row_no_blk_split", "res2_rows", "pack_scour", "pack_scour_nop"]
+         "rem", "rem_same_row", "rem_same_row_no_blk_split", "res2_rows", "pack_scour", "pack_scour_nop",
+         # a pack's shape: the sibling pass's second scour of the popped block changed it (not a no-op: a
+         # tombstone the first pass dropped lets its neighbours join); the other siblings the pass changed;
+         # packs with siblings in one row / two rows, with a sibling on the serial walk, with an arena_gc
+         # during the pass, cascading into pack_internal, with 8 siblings (none: a level-1 node splits at
+         # 8), ending with more blocks than siblings; the sums of siblings and of resulting blocks
+         "pack_self_changed", "pack_sib_changed", "pack_one_row", "pack_two_rows", "pack_serial", "pack_gc",
+         "pack_cascade", "pack_m8", "pack_grows", "pack_m_sum", "pack_kk_sum",
+         # needsScour marks: as a second write of the row the edit has just written / folded into that write
+         "lru_rewrite", "lru_folded"]
 
 
 def main():
@@ -57,6 +66,13 @@ def main():
         "removes_same_row_no_blk_split_share": round(st["rem_same_row_no_blk_split"] / max(st["rem"], 1), 4),
         "find_rows_per_pop": round(st["find_rows"] / max(st["pop"], 1), 3),
         "pack_scours_per_pack": round(st["pack_scour"] / max(st["pack"], 1), 3),
+        "pack_siblings_changed_per_pack": round(st["pack_sib_changed"] / max(st["pack"], 1), 3),
+        "pack_two_rows_share": round(st["pack_two_rows"] / max(st["pack"], 1), 4),
+        "pack_serial_share": round(st["pack_serial"] / max(st["pack"], 1), 4),
+        "pack_gc_share": round(st["pack_gc"] / max(st["pack"], 1), 6),
+        "pack_cascade_share": round(st["pack_cascade"] / max(st["pack"], 1), 4),
+        "pack_siblings_mean": round(st["pack_m_sum"] / max(st["pack"], 1), 3),
+        "pack_blocks_out_mean": round(st["pack_kk_sum"] / max(st["pack"], 1), 3),
         # a settle half on a second wave: of the ops after one whose settle pops, the
         # share whose first resolve would have to be repeated, and the rows a popping settle rewrites
         "duo_redo_share": round(st["duo_spec_redo"] / max(st["duo_spec_ok"] + st["duo_spec_redo"], 1), 4),
