@@ -19,6 +19,7 @@
 #include "ck_plan.hpp"
 #include "engine_types.hpp"
 #include "host_batch.hpp"
+#include "view.h"
 
 #pragma GCC visibility push(hidden)
 template <class T>
@@ -242,6 +243,14 @@ struct mte_engine {
                                              // e->order / e->cfg
     hipEvent_t ev_blk = nullptr;             // k_blk_ck done (second stream)
 
+    // ---- view queries (view.cpp): the plan's and the results' device buffers, grown as calls need them
+    // and kept across calls
+    DevBuf<ViewGroup> d_vgroups;
+    DevBuf<ViewProbeRec> d_vrec;
+    DevBuf<ViewCopyJob> d_vjobs;
+    DevBuf<uint32_t> d_vpos, d_vtotals;
+    DevBuf<uint16_t> d_vtext;
+
     // ---- last load and last run
     bool replayed = false;
     std::vector<DocRes> res;
@@ -326,6 +335,7 @@ int read_counters(mte_engine* e, uint32_t* ctr, uint32_t n);
 int ensure_download(mte_engine* e);
 int ensure_emit_download(mte_engine* e);
 int fetch_map_record(mte_engine* e, uint32_t d, uint32_t id, uint32_t* w);
+int fetch_out_row_map(mte_engine* e, uint64_t row, bool& has, uint32_t* w);
 int fetch_handle_table(mte_engine* e, uint32_t d, std::vector<uint32_t>& w);
 int fetch_cell_handles(mte_engine* e, std::vector<uint32_t>& h);
 int fetch_catch_up_records(mte_engine* e, uint32_t d, std::vector<uint4>& rec);

@@ -672,6 +672,17 @@ int fetch_map_record(mte_engine* e, uint32_t d, uint32_t id, uint32_t* w) {
     return MTE_OK;
 }
 
+// The property map of one row of the output pool (row: its index in the pool, inside the rows the pass
+// wrote): has = the row carries one, then its map_words words in w. Two small copies, no download.
+int fetch_out_row_map(mte_engine* e, uint64_t row, bool& has, uint32_t* w) {
+    HIP_TRY(e, hipSetDevice(e->device));
+    uint4 a;
+    HIP_TRY(e, hipMemcpy(&a, e->d_out_aux.p + row, sizeof a, hipMemcpyDeviceToHost));
+    has = a.x != 0 && e->P.out_maps;
+    if (has) HIP_TRY(e, hipMemcpy(w, e->d_out_maps.p + row * e->map_words, e->map_words * 4, hipMemcpyDeviceToHost));
+    return MTE_OK;
+}
+
 // The words of document d's HandleTable region (Params::htab), w.size() of them.
 int fetch_handle_table(mte_engine* e, uint32_t d, std::vector<uint32_t>& w) {
     HIP_TRY(e, hipMemcpy(w.data(), e->d_htab.p + e->cfg[d].ht_off, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));

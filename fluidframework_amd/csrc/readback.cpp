@@ -73,8 +73,8 @@ struct DocView {
     // SegView::props: 1 + the row's index in the output pool (its map was copied there), 0 = none
     const uint32_t* map(uint32_t id) const { return e->h_maps.data() + (uint64_t)(id - 1) * e->map_words; }
     // JSON of a property map in JS key order (integer-like keys ascending first, then insertion order)
-    void props_json(std::string& o, uint32_t id) const {
-        const uint32_t* m = map(id);
+    void props_json(std::string& o, uint32_t id) const { props_json(o, map(id)); }
+    void props_json(std::string& o, const uint32_t* m) const {
         uint32_t n = m[0];
         std::vector<std::pair<uint32_t, uint32_t>> idx;
         std::vector<uint32_t> rest;
@@ -197,6 +197,34 @@ int mte_length(mte_engine* e, uint32_t doc, uint64_t* len) {
     for (auto& sg : v.segs)
         if (!sg.removed) n += sg.len;  // a marker counts 1 (Marker.cachedLength, mergeTree.ts:649)
     if (len) *len = n;
+    return MTE_OK;
+}
+
+int mte_view_props(mte_engine* e, uint32_t doc, uint32_t row, char* buf, size_t cap, size_t* len) {
+    if (!e) return MTE_E_ARG;
+    if (!e->replayed) return set_err(e, MTE_E_STATE, "no replay results yet");
+    if (doc >= e->res.size()) return set_err(e, MTE_E_RANGE, "doc index out of range");
+    const DocRes& r = e->res[doc];
+    if (r.status) return set_err(e, MTE_E_STATE, "the document's replay failed");
+    uint32_t ctr[2];
+    if (int rc = read_counters(e, ctr, 2)) return rc;
+    if (row >= r.n_segs || (uint64_t)r.out_off + r.n_segs > std::min<uint64_t>(ctr[1], e->P.out_cap))
+        return set_err(e, MTE_E_RANGE, "row index out of range");
+    std::vector<uint32_t> w(e->map_words);
+    bool has = false;
+    if (int rc = fetch_out_row_map(e, (uint64_t)r.out_off + row, has, w.data())) return rc;
+    std::string o = "null";
+    if (has) {
+        DocView v;
+        v.e = e;
+        v.d = doc;
+        o.clear();
+        v.props_json(o, w.data());
+    }
+    if (len) *len = o.size();
+    if (!buf) return MTE_OK;
+    if (cap < o.size()) return MTE_E_RANGE;
+    memcpy(buf, o.data(), o.size());
     return MTE_OK;
 }
 

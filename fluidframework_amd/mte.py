@@ -98,6 +98,17 @@ class mte_doc_summary(ctypes.Structure):
 SUMMARY_DTYPE = np.dtype([("checksum", "<u8"), ("ops", "<u4"), ("length", "<u4"), ("segments", "<u4"),
                           ("snapshot_bytes", "<u4"), ("status", "<i4"), ("doc_id", "<u4")])
 
+# View queries (mte_views): the query and result records, and their constants.
+VIEW_Q_DTYPE = np.dtype([("doc", "<u4"), ("ref_seq", "<i4"), ("client", "<u4"), ("kind", "<u4"), ("pos1", "<u4"),
+                         ("pos2", "<u4")])
+VIEW_R_DTYPE = np.dtype([("status", "<i4"), ("row", "<u4"), ("offset", "<u4"), ("length", "<u4"), ("cur_pos", "<u4"),
+                         ("flags", "<u4"), ("text_off", "<u8")])
+assert VIEW_Q_DTYPE.itemsize == 24 and VIEW_R_DTYPE.itemsize == 32
+MTE_VQ_LENGTH, MTE_VQ_LOCATE, MTE_VQ_TEXT = 0, 1, 2
+MTE_VIEW_OK, MTE_VIEW_PAST_END, MTE_VIEW_OUT_OF_WINDOW, MTE_VIEW_DOC_FAILED, MTE_VIEW_BAD_QUERY = 0, 1, 2, 3, 4
+MTE_VIEW_NO_CLIENT = 0xFFFFFFFF
+MTE_VIEW_F_REMOVED = 1
+
 # Every symbol declared in include/mte.h (checked by tests/test_abi.py).
 EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mte_last_error", "mte_load",
            "mte_replay", "mte_generate", "mte_generate_ids", "mte_export_batch", "mte_doc_status", "mte_text", "mte_length", "mte_segments",
@@ -105,7 +116,7 @@ EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mt
            "mte_rccl_comm_create", "mte_rccl_comm_destroy", "mte_gather_summaries", "mte_gather_summaries_alloc", "mte_free", "mte_builder_create", "mte_builder_add_doc", "mte_builder_add_doc_from_summary", "mte_builder_add_container_log", "mte_builder_doc_path",
            "mte_builder_add_matrix_log", "mte_builder_add_matrix_from_summary", "mte_snapshot_matrix",
            "mte_builder_batch", "mte_builder_open_doc", "mte_builder_append_messages", "mte_retain",
-           "mte_builder_open_doc_from_summary",
+           "mte_builder_open_doc_from_summary", "mte_views", "mte_client_slot", "mte_view_props",
            "mte_builder_error", "mte_builder_destroy"]
 
 _lib = None
@@ -173,6 +184,10 @@ def lib():
         if hasattr(L, "mte_builder_open_doc_from_summary"):
             L.mte_builder_open_doc_from_summary.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, sz,
                                                             ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "mte_views"):  # (A/B runs load older experiment builds)
+            L.mte_views.argtypes = [vp, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
+            L.mte_client_slot.argtypes = [vp, u32, ctypes.c_char_p, ctypes.POINTER(u32)]
+            L.mte_view_props.argtypes = [vp, u32, u32, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
         L.mte_builder_error.argtypes = [vp]
         L.mte_builder_error.restype = ctypes.c_char_p
         L.mte_builder_destroy.argtypes = [vp]
@@ -378,6 +393,37 @@ class Engine:
         self._check(lib().mte_length(self._h, doc, ctypes.byref(n)), "mte_length")
         return n.value
 
+    def views(self, queries):
+        """mte_views: positional reads in any client's view, on the GPU, without the whole-batch
+        download. queries: a VIEW_Q_DTYPE array, or an iterable of (doc, ref_seq, client, kind, pos1, pos2).
+        Returns (results: VIEW_R_DTYPE array in query order, text: uint16 array of the TEXT queries'
+        units; result i's text is text[text_off : text_off + length])."""
+        if not (isinstance(queries, np.ndarray) and queries.dtype == VIEW_Q_DTYPE):
+            queries = np.array([tuple(int(x) for x in t) for t in queries], dtype=VIEW_Q_DTYPE)
+        q = np.ascontiguousarray(queries)
+        out = np.zeros(len(q), dtype=VIEW_R_DTYPE)
+        n = ctypes.c_size_t()
+        self._check(lib().mte_views(self._h, q.ctypes.data, len(q), out.ctypes.data, None, 0, ctypes.byref(n)), "mte_views")
+        text = np.zeros(n.value, dtype=np.uint16)
+        if n.value:
+            self._check(lib().mte_views(self._h, q.ctypes.data, len(q), out.ctypes.data, text.ctypes.data, n.value,
+                                        ctypes.byref(n)), "mte_views")
+        return out, text
+
+    def client_slot(self, doc, name):
+        """The short id of long client id `name` in document doc, MTE_VIEW_NO_CLIENT when it has none."""
+        s = ctypes.c_uint32()
+        self._check(lib().mte_client_slot(self._h, doc, name.encode(), ctypes.byref(s)), "mte_client_slot")
+        return s.value
+
+    def view_props(self, doc, row):
+        """The property object of row `row` (a LOCATE result's) of document doc, or None."""
+        n = ctypes.c_size_t()
+        self._check(lib().mte_view_props(self._h, doc, row, None, 0, ctypes.byref(n)), "mte_view_props")
+        buf = ctypes.create_string_buffer(n.value + 1)
+        self._check(lib().mte_view_props(self._h, doc, row, buf, n.value + 1, ctypes.byref(n)), "mte_view_props")
+        return json.loads(buf.raw[: n.value].decode("utf-8"))
+
     def _str_call(self, fn, doc, *extra):
         n = ctypes.c_size_t()
         self._check(fn(self._h, doc, None, 0, ctypes.byref(n), *extra), fn.__name__)
@@ -556,8 +602,51 @@ class MergeTreeClient:
         e = self._run()
         return e.get_info("resumed_ops") + e.get_info("resumed_ops_blk")
 
-    def getText(self):  # noqa: N802
-        return self._run().text(0)
+    def getText(self, start=None, end=None):  # noqa: N802
+        """The whole text, or with start / end MergeTreeTextHelper.getText's range (textSegment.ts:154-186)
+        in the current view, read on the GPU."""
+        e = self._run()
+        if start is None and end is None:
+            return e.text(0)
+        r, t = e.views([(0, 0, 0, MTE_VQ_TEXT, start or 0, 0xFFFFFFFF if end is None else max(end, start or 0))])
+        return t.tobytes().decode("utf-16-le", "surrogatepass")
+
+    def _locate(self, pos):
+        r, _ = self._run().views([(0, 0, 0, MTE_VQ_LOCATE, pos, 0)])
+        return r[0]
+
+    def getContainingSegment(self, pos):  # noqa: N802
+        """(row, offset) of the segment at pos in the current view -- row indexes the segment table --
+        or (None, None) past the end (client.ts:1022-1031)."""
+        r = self._locate(pos)
+        return (int(r["row"]), int(r["offset"])) if r["status"] == MTE_VIEW_OK else (None, None)
+
+    def getPropertiesAtPosition(self, pos):  # noqa: N802
+        """The properties of the segment at pos, or None (client.ts:1012-1020)."""
+        r = self._locate(pos)
+        return self._engine.view_props(0, int(r["row"])) if r["status"] == MTE_VIEW_OK else None
+
+    def getPosition(self, row):  # noqa: N802
+        """The current position of segment table row `row` (client.ts:295-300): the start of the first
+        visible row at or after it, found by locating positions (O(log length) queries)."""
+        e = self._run()
+        r, _ = e.views([(0, 0, 0, MTE_VQ_LENGTH, 0, 0)])
+        lo, hi = 0, int(r[0]["length"])
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if int(self._locate(mid)["row"]) >= row:
+                hi = mid
+            else:
+                lo = mid + 1
+        return lo
+
+    def getLengthAt(self, refSeq, clientId):  # noqa: N802,N803
+        """MergeTree.getLength(refSeq, clientId) (mergeTree.ts:1577-1584) for a long client id."""
+        e = self._run()
+        r, _ = e.views([(0, refSeq, e.client_slot(0, clientId), MTE_VQ_LENGTH, 0, 0)])
+        if r[0]["status"] != MTE_VIEW_OK:
+            raise MteError(f"getLengthAt: view status {int(r[0]['status'])}")
+        return int(r[0]["length"])
 
     def getLength(self):  # noqa: N802
         return self._run().length(0)

@@ -328,6 +328,62 @@ int mte_snapshot_matrix(mte_engine* e, uint32_t rows_doc, uint32_t cols_doc, cha
 /* Per-doc summaries for all docs of the batch (checksum over text + snapshot blobs). */
 int mte_summaries(mte_engine* e, mte_doc_summary* out, size_t cap);
 
+/* ---- view queries ------------------------------------------------------------------------------
+ * Positional reads of the replayed documents as ANY client saw them, answered on the GPU from the
+ * pass's output rows, many documents a call, without the whole-batch download the reads above make.
+ * A view is (ref_seq, client): client = a short id of the document (mte_client_slot), 0 = the
+ * observer (the local view; ref_seq unused, as for a non-collaborating document), or
+ * MTE_VIEW_NO_CLIENT = a client that owns no slot of the document (all its ops at or below minSeq).
+ * A row's length in a view is nodeLength (mergeTree.ts:1659-1699). Positions and lengths are UTF-16
+ * units, a marker counting 1. */
+#define MTE_VIEW_NO_CLIENT 0xFFFFFFFFu
+enum {
+    MTE_VQ_LENGTH = 0,  /* MergeTree.getLength(refSeq, clientId) (mergeTree.ts:1577-1584): length */
+    MTE_VQ_LOCATE = 1,  /* getContainingSegment(pos1) (mergeTree.ts:1623-1634, searchBlock :1797-1829): row = index
+                           in mte_segments order of the first row whose cumulative view length exceeds pos1,
+                           offset = pos1 - the row's start in the view, length = the row's length, cur_pos =
+                           Client.getPosition(segment) (client.ts:295-300, mergeTree.ts:1586-1603): the
+                           observer-visible units before the row */
+    MTE_VQ_TEXT = 2,    /* MergeTreeTextHelper.getText(refSeq, clientId, "", pos1, pos2) (textSegment.ts:154-186):
+                           the units of the view's text rows in [pos1, min(pos2, view length)), markers and
+                           permutation runs adding nothing: text[text_off .. text_off + length) */
+};
+enum {                            /* mte_view_r.status; none of them fails the call */
+    MTE_VIEW_OK = 0,
+    MTE_VIEW_PAST_END = 1,        /* LOCATE: pos1 >= the view's length (the reference: segment undefined); length =
+                                     the view's length */
+    MTE_VIEW_OUT_OF_WINDOW = 2,   /* client != 0 and ref_seq outside [minSeq, currentSeq] of the document */
+    MTE_VIEW_DOC_FAILED = 3,      /* the document's replay status is not MTE_DOC_OK */
+    MTE_VIEW_BAD_QUERY = 4,       /* doc or client out of range, unknown kind, pos2 < pos1 */
+};
+#define MTE_VIEW_F_REMOVED 0x1u   /* LOCATE: the row is removed in the observer's view: the position transformed to
+                                     the current view is cur_pos, else cur_pos + offset */
+typedef struct mte_view_q {
+    uint32_t doc;
+    int32_t ref_seq;
+    uint32_t client;
+    uint32_t kind;        /* MTE_VQ_* */
+    uint32_t pos1, pos2;  /* pos2: TEXT only */
+} mte_view_q;
+typedef struct mte_view_r {       /* 32 bytes */
+    int32_t status;               /* MTE_VIEW_* */
+    uint32_t row, offset, length, cur_pos, flags;
+    uint64_t text_off;            /* TEXT: first unit in the call's text buffer */
+} mte_view_r;
+/* Client.getLength / getContainingSegment / getPosition / MergeTreeTextHelper.getText in the view of
+ * any client (client.ts:295-300, 1012-1031; above): out[i] answers q[i]. The TEXT queries' units go to
+ * text (text_cap units; *text_len = the units they need). text may be NULL to size the buffer; a
+ * text_cap too small is MTE_E_RANGE with *text_len set. MTE_E_STATE before a replay. */
+int mte_views(mte_engine* e, const mte_view_q* q, size_t n, mte_view_r* out, uint16_t* text, size_t text_cap,
+              size_t* text_len);
+/* Client.getOrAddShortClientId's table read (client.ts:644-668): the short id of long id client_id in
+ * document doc, MTE_VIEW_NO_CLIENT when it has none. */
+int mte_client_slot(mte_engine* e, uint32_t doc, const char* client_id, uint32_t* slot);
+/* Client.getPropertiesAtPosition's read of segment.properties (client.ts:1012-1020) for row `row` of
+ * document doc (a LOCATE's row): the property object as JSON text, "null" for none. Fetches that
+ * row's map record alone. buf may be NULL to query *len. */
+int mte_view_props(mte_engine* e, uint32_t doc, uint32_t row, char* buf, size_t cap, size_t* len);
+
 /* Multi-GPU: documents are sharded by id across ranks (one process per GPU) and the
  * only collective of the path is this all-gather of the per-document summary records, over RCCL
  * (xGMI inside a node). The communicator is RCCL's own: rank 0 makes an id (mte_rccl_unique_id),

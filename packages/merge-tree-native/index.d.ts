@@ -3,6 +3,24 @@ import { ISequencedDocumentMessage, ITree } from "@fluidframework/protocol-defin
 
 export declare const DocStatus: { Ok: 0; InsertFailed: 1; SequenceOrder: 2; Capacity: 3; Unsupported: 4 };
 
+/** View queries (BatchedMergeEngine.views): what to read, and how each query ended. */
+export declare const ViewKind: { Length: 0; Locate: 1; Text: 2 };
+export declare const ViewStatus: { Ok: 0; PastEnd: 1; OutOfWindow: 2; DocFailed: 3; BadQuery: 4 };
+/** `client` of a view for a client that owns no slot of the document (all its ops at or below minSeq). */
+export declare const VIEW_NO_CLIENT: number;
+export declare const VIEW_F_REMOVED: number;
+/** One positional read in the view (refSeq, client) of a document. client: a short id (clientSlot), 0 or
+ *  omitted = the observer (refSeq unused), VIEW_NO_CLIENT. pos2 (Text only) defaults to the view's end. */
+export interface ViewQuery { doc: number; refSeq: number; client?: number; kind: 0 | 1 | 2; pos1?: number; pos2?: number; }
+/** Length: length = MergeTree.getLength(refSeq, client). Locate: row (index in the segment table) / offset /
+ *  length of getContainingSegment(pos1), curPos = Client.getPosition of that segment, removed = it is
+ *  removed in the current view (the position then maps to curPos, else to curPos + offset); status PastEnd
+ *  (length = the view's length) when pos1 is not inside the view. Text: text =
+ *  MergeTreeTextHelper.getText(refSeq, client, "", pos1, pos2). status OutOfWindow: refSeq outside
+ *  [minSeq, currentSeq]; DocFailed; BadQuery. */
+export interface ViewResult { status: number; row: number; offset: number; length: number; curPos: number;
+    removed: boolean; text?: string; }
+
 export interface ReplayStats { docs: number; ops: number; messages: number; failedDocs: number; kernelMs: number; }
 export interface DocSummary {
     checksum: bigint | string; ops: number; length: number; segments: number;
@@ -41,8 +59,16 @@ export declare class BatchedMergeEngine {
     retain(on?: boolean): void;
     /** op records the last replay continued past instead of replaying (mte_get_info "resumed_ops") */
     resumedOps(): number;
-    /** mte_get_info: routing and counters of the last pass ("resumed_docs", "rows", "solo", ...) */
+    /** mte_get_info: routing and counters of the last pass ("resumed_docs", "rows", "solo", ...;
+     *  "downloaded": 1 once a whole-batch read such as getText(doc) has copied the results to the host) */
     getInfo(key: string): number;
+    /** mte_views: many positional reads, any document, any client's view, answered on the GPU from the last
+     *  replay's rows in one call, without copying the batch's results to the host. results[i] answers queries[i]. */
+    views(queries: ViewQuery[]): ViewResult[];
+    /** mte_client_slot: the short id of a long client id in a document, VIEW_NO_CLIENT when it has none. */
+    clientSlot(doc: number, clientId: string): number;
+    /** mte_view_props: the properties of segment table row `row` of a document, or null. */
+    viewProps(doc: number, row: number): Record<string, unknown> | null;
 }
 
 /** An RCCL communicator handle (released by rcclCommDestroy or when collected). */
@@ -61,8 +87,17 @@ export declare class MergeTreeClient {
     applyMsgs(msgs: ISequencedDocumentMessage[]): void;
     /** Replay the staged messages off the event loop. */
     flush(): Promise<void>;
-    getText(): string;
+    /** The whole text; with start / end, the range [start, end) of the current view. */
+    getText(start?: number, end?: number): string;
     getLength(): number;
+    /** Client.getContainingSegment: segment = the row of the segment table; both undefined past the end. */
+    getContainingSegment(pos: number): { segment: number | undefined; offset: number | undefined };
+    /** Client.getPropertiesAtPosition */
+    getPropertiesAtPosition(pos: number): Record<string, unknown> | undefined;
+    /** Client.getPosition of segment table row `row` */
+    getPosition(row: number): number;
+    /** MergeTree.getLength(refSeq, clientId), clientId the long id */
+    getLengthAt(refSeq: number, clientId: string): number;
     snapshot(): ITree;
     /** op records the last read did not replay again */
     resumedOps(): number;

@@ -11,6 +11,11 @@ const path = require("path");
 const addon = require(path.join(__dirname, "build", "mte_native.node"));
 
 const DocStatus = Object.freeze({ Ok: 0, InsertFailed: 1, SequenceOrder: 2, Capacity: 3, Unsupported: 4 });
+/** View queries (mte_views): kinds, per-query statuses, the client that owns no slot, the LOCATE flag. */
+const ViewKind = Object.freeze({ Length: 0, Locate: 1, Text: 2 });
+const ViewStatus = Object.freeze({ Ok: 0, PastEnd: 1, OutOfWindow: 2, DocFailed: 3, BadQuery: 4 });
+const VIEW_NO_CLIENT = 0xFFFFFFFF;
+const VIEW_F_REMOVED = 1;
 
 class BatchedMergeEngine {
     constructor(options = {}) {
@@ -82,6 +87,42 @@ class BatchedMergeEngine {
     getLength(doc) { this._idle(); return addon.getLength(this._engine, doc); }
     docStatus(doc) { this._idle(); return addon.docStatus(this._engine, doc); }
     getText(doc) { this._idle(); return addon.getText(this._engine, doc); }
+    /**
+     * mte_views: positional reads in any client's view, answered on the GPU from the last replay's rows
+     * without downloading the batch. queries: [{ doc, refSeq, client, kind, pos1, pos2 }] -- client a short
+     * id (clientSlot), 0 = the observer, VIEW_NO_CLIENT = a client without a slot. Returns, in query order,
+     * [{ status, row, offset, length, curPos, removed, text? }]: Length -> length (getLength(refSeq, client));
+     * Locate -> row / offset / length (getContainingSegment), curPos (getPosition), removed; Text -> text
+     * (MergeTreeTextHelper.getText(refSeq, client, "", pos1, pos2)).
+     */
+    views(queries) {
+        this._idle();
+        const qb = Buffer.alloc(queries.length * 24);
+        queries.forEach((q, i) => {
+            qb.writeUInt32LE(q.doc >>> 0, i * 24);
+            qb.writeInt32LE(q.refSeq | 0, i * 24 + 4);
+            qb.writeUInt32LE((q.client === undefined ? 0 : q.client) >>> 0, i * 24 + 8);
+            qb.writeUInt32LE(q.kind >>> 0, i * 24 + 12);
+            qb.writeUInt32LE((q.pos1 || 0) >>> 0, i * 24 + 16);
+            qb.writeUInt32LE((q.pos2 === undefined ? 0xFFFFFFFF : q.pos2) >>> 0, i * 24 + 20);
+        });
+        const [rb, tb] = addon.views(this._engine, qb);
+        return queries.map((q, i) => {
+            const o = i * 32;
+            const r = { status: rb.readInt32LE(o), row: rb.readUInt32LE(o + 4), offset: rb.readUInt32LE(o + 8),
+                length: rb.readUInt32LE(o + 12), curPos: rb.readUInt32LE(o + 16),
+                removed: (rb.readUInt32LE(o + 20) & VIEW_F_REMOVED) !== 0 };
+            if (q.kind === ViewKind.Text && r.status === ViewStatus.Ok) {
+                const at = Number(rb.readBigUInt64LE(o + 24));
+                r.text = tb.toString("utf16le", at * 2, (at + r.length) * 2);
+            }
+            return r;
+        });
+    }
+    /** mte_client_slot: the short id of a long client id in a document, VIEW_NO_CLIENT when it has none */
+    clientSlot(doc, name) { this._idle(); return addon.clientSlot(this._engine, doc, name); }
+    /** mte_view_props: the property object of row `row` (a Locate result's) of a document, or null */
+    viewProps(doc, row) { this._idle(); return JSON.parse(addon.viewProps(this._engine, doc, row)); }
     /** The ITree SnapshotV1.emit(serializer) returns: { entries: [...], id: null } */
     snapshotV1(doc) { this._idle(); return JSON.parse(addon.snapshotV1(this._engine, doc)); }
     /** SharedMatrix summary of a { matrix } document pair (its rows and cols PermutationVectors) */
@@ -207,7 +248,48 @@ class MergeTreeClient {
     }
     /** op records the last read continued past instead of replaying again */
     resumedOps() { this._run(); return this._engine.resumedOps(); }
-    getText() { return this._run().getText(0); }
+    /** The whole text, or with start / end the range [start, end) of the current view
+     *  (MergeTreeTextHelper.getText, textSegment.ts:154-186), read on the GPU. */
+    getText(start, end) {
+        const e = this._run();
+        if (start === undefined && end === undefined) return e.getText(0);
+        const s = start || 0;
+        return e.views([{ doc: 0, refSeq: 0, client: 0, kind: ViewKind.Text, pos1: s,
+            pos2: end === undefined ? 0xFFFFFFFF : Math.max(end, s) }])[0].text;
+    }
+    _locate(pos) { return this._run().views([{ doc: 0, refSeq: 0, client: 0, kind: ViewKind.Locate, pos1: pos }])[0]; }
+    /** Client.getContainingSegment (client.ts:1022-1031): { segment: row of the segment table, offset },
+     *  both undefined past the end. */
+    getContainingSegment(pos) {
+        const r = this._locate(pos);
+        return r.status === ViewStatus.Ok ? { segment: r.row, offset: r.offset } : { segment: undefined, offset: undefined };
+    }
+    /** Client.getPropertiesAtPosition (client.ts:1012-1020): the segment's properties, or undefined. */
+    getPropertiesAtPosition(pos) {
+        const r = this._locate(pos);
+        if (r.status !== ViewStatus.Ok) return undefined;
+        const p = this._engine.viewProps(0, r.row);
+        return p === null ? undefined : p;
+    }
+    /** Client.getPosition (client.ts:295-300) of segment table row `row`: the start of the first visible
+     *  row at or after it (found by locating positions: O(log length) queries). */
+    getPosition(row) {
+        const e = this._run();
+        let lo = 0, hi = e.views([{ doc: 0, refSeq: 0, client: 0, kind: ViewKind.Length }])[0].length;
+        while (lo < hi) {
+            const mid = (lo + hi) >>> 1;
+            const r = e.views([{ doc: 0, refSeq: 0, client: 0, kind: ViewKind.Locate, pos1: mid }])[0];
+            if (r.row >= row) hi = mid; else lo = mid + 1;
+        }
+        return lo;
+    }
+    /** MergeTree.getLength(refSeq, clientId) (mergeTree.ts:1577-1584) for a long client id. */
+    getLengthAt(refSeq, clientId) {
+        const e = this._run();
+        const r = e.views([{ doc: 0, refSeq, client: e.clientSlot(0, clientId), kind: ViewKind.Length }])[0];
+        if (r.status !== ViewStatus.Ok) throw new Error(`getLengthAt: view status ${r.status}`);
+        return r.length;
+    }
     /** Client.getLength (client.ts:1057): markers count 1, unlike getText().length. */
     getLength() { return this._run().getLength(0); }
     /** Client.snapshot (client.ts:907-942): SnapshotV1, or SnapshotLegacy with its catch-up messages
@@ -219,7 +301,7 @@ class MergeTreeClient {
 }
 
 module.exports = {
-    BatchedMergeEngine, MergeTreeClient, DocStatus,
+    BatchedMergeEngine, MergeTreeClient, DocStatus, ViewKind, ViewStatus, VIEW_NO_CLIENT, VIEW_F_REMOVED,
     abiVersion: addon.abiVersion, buildInfo: addon.buildInfo,
     createBuilder: addon.createBuilder, builderAddDoc: addon.builderAddDoc, builderDocCount: addon.builderDocCount,
     builderOpenDoc: addon.builderOpenDoc, builderAppendMessages: addon.builderAppendMessages,

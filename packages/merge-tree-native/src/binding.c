@@ -646,6 +646,83 @@ static napi_value js_gather_summaries(napi_env env, napi_callback_info info) {
     return buf;
 }
 
+/* views(engine, queries: Buffer of mte_view_q records): [results: Buffer of mte_view_r records, text: Buffer
+ * of UTF-16 units] -- mte_views, the sizing call and then the real one */
+static napi_value js_views(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    mte_engine* e = (mte_engine*)get_external(env, argv[0]);
+    void* qbuf = NULL;
+    size_t qlen = 0;
+    if (napi_get_buffer_info(env, argv[1], &qbuf, &qlen) != napi_ok || qlen % sizeof(mte_view_q))
+        return throw_mte(env, "views", MTE_E_ARG, "queries: a Buffer of 24-byte records");
+    const size_t n = qlen / sizeof(mte_view_q);
+    mte_view_q* q = (mte_view_q*)malloc(qlen + 1);  /* (a Buffer's bytes need not be aligned) */
+    mte_view_r* out = (mte_view_r*)calloc(n + 1, sizeof(mte_view_r));
+    if (!q || !out) {
+        free(q);
+        free(out);
+        return throw_mte(env, "views", MTE_E_NOMEM, NULL);
+    }
+    memcpy(q, qbuf, qlen);
+    size_t units = 0;
+    uint16_t* text = NULL;
+    int rc = mte_views(e, q, n, out, NULL, 0, &units);
+    if (!rc && units) {
+        text = (uint16_t*)malloc(units * 2);
+        rc = text ? mte_views(e, q, n, out, text, units, &units) : MTE_E_NOMEM;
+    }
+    napi_value arr = NULL, rb, tb;
+    if (!rc) {
+        if (napi_create_array_with_length(env, 2, &arr) != napi_ok ||
+            napi_create_buffer_copy(env, n * sizeof(mte_view_r), out, NULL, &rb) != napi_ok ||
+            napi_create_buffer_copy(env, units * 2, text ? (void*)text : (void*)out, NULL, &tb) != napi_ok)
+            rc = MTE_E_NOMEM;
+    }
+    free(q);
+    free(out);
+    free(text);
+    if (rc) return throw_mte(env, "mte_views", rc, e ? mte_last_error(e) : NULL);
+    napi_set_element(env, arr, 0, rb);
+    napi_set_element(env, arr, 1, tb);
+    return arr;
+}
+
+/* clientSlot(engine, doc, clientId): number -- the short id, 0xFFFFFFFF when the document has none for it */
+static napi_value js_client_slot(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    mte_engine* e = (mte_engine*)get_external(env, argv[0]);
+    uint32_t d, slot = 0;
+    napi_get_value_uint32(env, argv[1], &d);
+    char* name = get_string(env, argv[2], NULL);
+    if (!name) return throw_mte(env, "clientSlot", MTE_E_ARG, "clientId: a string");
+    int rc = mte_client_slot(e, d, name, &slot);
+    free(name);
+    if (rc) return throw_mte(env, "mte_client_slot", rc, e ? mte_last_error(e) : NULL);
+    return make_u32(env, slot);
+}
+
+/* viewProps(engine, doc, row): string -- the row's property object as JSON, "null" for none */
+static napi_value js_view_props(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    mte_engine* e = (mte_engine*)get_external(env, argv[0]);
+    uint32_t d, row;
+    napi_get_value_uint32(env, argv[1], &d);
+    napi_get_value_uint32(env, argv[2], &row);
+    size_t n = 0;
+    int rc = mte_view_props(e, d, row, NULL, 0, &n);
+    if (rc) return throw_mte(env, "mte_view_props", rc, e ? mte_last_error(e) : NULL);
+    char* buf = (char*)malloc(n + 1);
+    rc = buf ? mte_view_props(e, d, row, buf, n, &n) : MTE_E_NOMEM;
+    napi_value s = NULL;
+    if (!rc) napi_create_string_utf8(env, buf, n, &s);
+    free(buf);
+    if (rc) return throw_mte(env, "mte_view_props", rc, mte_last_error(e));
+    return s;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
     napi_property_descriptor props[] = {
         {"abiVersion", 0, js_abi_version, 0, 0, 0, napi_default, 0},
@@ -677,6 +754,9 @@ static napi_value init(napi_env env, napi_value exports) {
         {"rcclCommCreate", 0, js_rccl_comm_create, 0, 0, 0, napi_default, 0},
         {"rcclCommDestroy", 0, js_rccl_comm_destroy, 0, 0, 0, napi_default, 0},
         {"gatherSummaries", 0, js_gather_summaries, 0, 0, 0, napi_default, 0},
+        {"views", 0, js_views, 0, 0, 0, napi_default, 0},
+        {"clientSlot", 0, js_client_slot, 0, 0, 0, napi_default, 0},
+        {"viewProps", 0, js_view_props, 0, 0, 0, napi_default, 0},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;
