@@ -91,6 +91,7 @@ int mte_get_info(mte_engine* e, const char* key, int64_t* value) {
     else if (k == "slot_bytes") *value = (int64_t)e->P.slot_bytes;
     else if (k == "slots") *value = e->n_slots;
     else if (k == "solo") *value = e->last_solo;
+    else if (k == "solo_planned") *value = e->P.n_solo;  // the current slot plan's (set by the load, again by each pass)
     else if (k == "solo_us") *value = (int64_t)(e->last_solo_ms * 1000.0);  // the solo workgroups' pass (critical path)
     else if (k == "solo_lead_us") *value = (int64_t)(e->last_solo_lead_ms * 1000.0);
     else if (k == "solo_cycles") *value = (int64_t)e->last_solo_cycles;  // longest document's wave: s_memtime

@@ -523,6 +523,7 @@ int mte_load(mte_engine* e, const mte_batch* b) {
     e->host_ops_valid = false;
     e->replayed = e->downloaded = false;
     e->stage_copy_ms = e->stage_wait_ms = 0;
+    e->P.cell_mode = 0;  // (the last replay's pass number is not this batch's: solo_count reads it)
     const uint32_t nd = b->n_docs;
     std::vector<uint64_t> n_ops(nd), pay(nd), pi(nd), an(nd);
     std::vector<uint8_t> collab(nd), has_nl(nd, 0), not_lean(nd, 0), doc_ext(nd, 0), doc_cu(nd, 0), not_rows(nd, 0),
@@ -591,6 +592,11 @@ int mte_load(mte_engine* e, const mte_batch* b) {
     }
     auto t0 = std::chrono::steady_clock::now();
     int rc;
+    // which documents carry cell records, before the layout: its slot plan asks solo_count, which
+    // keeps them out of k_solo (load_cells fills in the records; the last load's set must not answer)
+    e->cell_recs.clear();
+    for (uint32_t d = 0; d < nd; d++)
+        if (n_cell[d]) e->cell_recs[d];
     if ((rc = layout_and_alloc(e, n_ops, pay, pi, an, collab, has_nl, 0, b->doc_op_offsets, b->doc_payload_offsets)))
         return rc;
     e->last_alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -681,6 +687,7 @@ int mte_generate_ids(mte_engine* e, uint32_t kind, uint32_t n_docs, uint32_t n_o
     if (kind != 2 && kind != 3 && kind != 5) return set_err(e, MTE_E_ARG, "generator kind must be 2, 3 or 5");
     HIP_TRY(e, hipSetDevice(e->device));
     e->ck.reset();  // (a new batch: no checkpoint of the last one may be continued)
+    e->P.cell_mode = 0;
     e->hb = HostBatch();
     uint32_t nps = build_generator_props(e);
     std::vector<uint64_t> nops(n_docs), pay(n_docs), pi(n_docs), an(n_docs);

@@ -76,6 +76,9 @@ void wave_plan(const mte_engine* e, uint32_t nd, uint32_t& groups, uint32_t& hbm
 uint32_t solo_count(const mte_engine* e) {
     const uint32_t nd = (uint32_t)e->order.size();
     if (!nd || !e->solo_max || e->force_hbm) return 0;
+    // pass 1 of a SharedMatrix batch lists its cell documents only (mte_replay): no solo workgroup,
+    // whatever the list's lengths look like against the whole batch's mean
+    if (e->P.cell_mode == 1) return 0;
     uint64_t total = 0, nmax = 0;
     for (uint64_t n : e->n_ops_doc) {
         total += n;
