@@ -60,6 +60,7 @@ enum RgProf : u32 {
     RP_HEAP, RP_FIND_SEG, RP_PACK, RP_LRU, RP_OPS, RP_N_RESOLVE, RP_N_SCOUR, RP_N_SCOUR_CHANGED,
     RP_N_PACK, RP_N_POP, RP_N_SPLIT_BLK, RP_N_MOVE, RP_SPLIT_AT, RP_INS, RP_REM, RP_MSN, RP_ZAM_EDIT,
     RP_PACK_SIBS,  // pack's sibling pass (zamboni's loop of scours in front of pack_leaves); reported as "scour_chain"
+    RP_PACK_FUSED,  // the fused pack (pack_fused: both of the above in one pass); reported as "scour_write"
     RP_N
 };
 #if defined(MTE_PROFILE) && !defined(MTE_CPU)
@@ -123,7 +124,10 @@ enum RgStat : u32 {
     RS_PACK_CASCADE, RS_PACK_M8, RS_PACK_GROWS, RS_PACK_M_SUM, RS_PACK_KK_SUM,
     // needsScour marks (add_lru): written as a second write of the row the edit has just written, and
     // folded into the edit's own row write
-    RS_LRU_REWRITE, RS_LRU_FOLDED, RS_N
+    RS_LRU_REWRITE, RS_LRU_FOLDED,
+    // packs taken by pack_fused, and the ones it handed back before any side effect: a joining slot longer
+    // than GRANULARITY (the serial walk), fresh chunks that do not fit the arena (arena_gc)
+    RS_PACK_FUSED, RS_PACK_FUSED_FB_SERIAL, RS_PACK_FUSED_FB_GC, RS_N
 };
 inline u64 g_rg_stats[RS_N + 64];
 #define RG_STAT(i, n) (g_rg_stats[i] += (u64)(n))
@@ -164,6 +168,10 @@ inline RgDuoStat g_rg_duo;
     } while (0)
 #endif
 
+#ifndef MTE_FUSED_PACK
+#define MTE_FUSED_PACK 1  // RegEngine::kFusedPack
+#endif
+
 struct RSeg {
     u32 len;
     i32 seq;
@@ -202,6 +210,10 @@ struct RegEngine {
     // builds spilling 19-25 VGPRs more at their 168-register bound -- and they keep add_lru's second
     // write of the row.
     static constexpr bool kFoldLru = !PAGED && NR == (int)RG_ROWS;
+    // A pack decides all its siblings at once and gathers the kept slots by mask (pack_fused) on the same
+    // engines; elsewhere zamboni keeps the sibling loop of scours and pack_leaves.
+    // (MTE_FUSED_PACK=0 / 2 builds it into no / every engine: the unfused twin of the CPU suite, A/B libraries.)
+    static constexpr bool kFusedPack = MTE_FUSED_PACK == 2 || (MTE_FUSED_PACK == 1 && !PAGED && NR == (int)RG_ROWS);
     static constexpr u32 MAXC = WIDE ? 64u : 32u;  // client ids below this (rm, rm2)
     typedef simd::V V;
     typedef simd::B B;
@@ -1442,6 +1454,229 @@ struct RegEngine {
         LV.set(0, simd::writelane(LV.get(0), pi, kk));
         if (kk < 4 && height > 2) pack_internal(pi, 1);
     }
+    // pack_leaves' plan and scatter for the fused pack, below. (pack_leaves keeps its own text: with the two
+    // sharing these functions, k_rows kernels that never fuse came out with other register and spill counts
+    // than the parent's -- k_rows<4, PROPS, WIDE, CK> 490 spilled SGPRs for 429 with the scatter shared.)
+    // What a pack of T items in m blocks makes: kk = max(1, min(7, T/4)) blocks of `base` items, the first
+    // `extra` of them one more; false when there is no room for the blocks (the document has failed).
+    SD bool pack_plan(u32 m, u32 T, u32& kk, u32& base, u32& extra) {
+        RG_COUNT(RP_N_PACK, 1);
+        RG_STAT(RS_PACK, 1);
+        RG_DUO(packed = true);
+        kk = T / 4;
+        if (kk > 7) kk = 7;
+        if (kk < 1) kk = 1;
+        base = T / kk;
+        extra = T % kk;
+        RG_STAT(RS_PACK_KK_SUM, kk);
+        RG_STAT(RS_PACK_GROWS, kk > m);
+        RG_STAT(RS_PACK_CASCADE, kk < 4 && height > 2);
+        return ensure_blocks(n_lb + kk - m);
+    }
+    // The items of a pack (lane t of `t`: item t, needsScour bits clear) into blocks [k0, k0 + kk), the
+    // blocks after the m old ones moved behind them, level 1 updated and the cascade run.
+    SD void pack_place(u32 pi, u32 m, u32 k0, u32 kk, u32 base, u32 extra, const Row& t) {
+        const i32 d = (i32)kk - (i32)m;
+        shift_blocks(k0 + m, d);
+        // destination: block k0 + dj slot dq <- item dj*base + min(dj, extra) + dq
+        const u32 rA = k0 >> 3, rB = (k0 + kk - 1) >> 3;
+        for (u32 rr = rA; rr <= rB; rr++) {
+            const V G = L() + rr * 64;
+            const V blk = G >> 3;
+            const B inb = (blk >= k0) & (blk < k0 + kk);
+            const V dj = blk - k0, dq = G & 7u;
+            const V big = simd::sel(dj < extra, dj, simd::splat(extra));
+            const V nB = simd::sel(dj < extra, base + 1, simd::splat(base));
+            const B have = inb & (dq < nB);
+            const V ti = (dj * base + big + dq) & 63u;
+            Row w = rows.ldrow(rr);
+            auto put = [&](V& x, const V& tv) MTE_LI { x = simd::sel(have, simd::bperm(tv, ti), simd::sel(inb, 0u, x)); };
+            put(w.len, t.len);
+            put(w.seq, t.seq);
+            put(w.rseq, t.rseq);
+            put(w.meta, t.meta);
+            put(w.toff, t.toff);
+            put(w.cap, t.cap);
+            put(w.rm, t.rm);
+            put(w.sid, t.sid);
+            if constexpr (PROPS) put(w.props, t.props);
+            if constexpr (WIDE) put(w.rm2, t.rm2);
+            rows.strow(rr, w);
+        }
+        rows.drop_row();
+        n_lb = (u32)((i32)n_lb + d);
+        if (n_lb > max_lb) max_lb = n_lb;
+        LV.set(0, simd::writelane(LV.get(0), pi, kk));
+        if (kk < 4 && height > 2) pack_internal(pi, 1);
+    }
+    // ---- the fused pack (kFusedPack): the sibling pass and pack_leaves in one pass over the one or two
+    // rows that hold blocks [k0, k0 + m). scour's predicates are taken row-wide, as 64-bit lane masks
+    // restricted to the sibling lanes; the runs' heads take their new len / toff / cap in registers; the
+    // kept slots (not dropped, not joined) are pushed straight to their item lane. No sibling is
+    // compacted, stored and read again only to be taken apart. Results are scour's and pack_leaves', bit
+    // for bit: the heads are walked in sibling order, then head order, so every fresh chunk has the offset
+    // the sibling loop gives it.
+    //
+    // One row's share: scour's decisions for the sibling lanes `sib` of row w, then its runs. Out: the
+    // heads' new (len, toff, cap) in nlen / ntoff / ncap (the other lanes as they were); the text copies as
+    // (jdst, jlen) per slot lane (sources: w.toff); fresh chunks taken from `top` on, their sum added to
+    // `need`; dst, the item lane of every kept slot (nBefore + its rank among the row's kept slots; the
+    // other lanes fill the rest of the wave, so dst is a permutation), nkeep of them; chg, the lanes
+    // dropped or joined; serial: a joining slot is longer than GRANULARITY. Nothing is written. (The masks
+    // are done with before the next row starts: the replay loop has no scalar registers to spare.)
+    SD void pack_row(const Row& w, u64 sib, u32 nBefore, V& nlen, V& ntoff, V& ncap, V& jdst, V& jlen, V& dst, u32& nkeep,
+                     u64& chg, bool& serial, u32& top, u32& need) {
+        const u64 act = simd::ballot(w.len != 0u) & sib;
+        const u64 rem = act & simd::ballot(w.rseq != RSEQ_LIVE);
+        const u64 drop = rem & simd::ballot(simd::sle(w.rseq, minSeq));
+        const u64 st = act & ~rem & simd::ballot(simd::sle(w.seq, minSeq)) & simd::ballot((w.meta & F_MARKER) == 0u);
+        u64 join = st & (st << 1) & ~0x0101010101010101ull;  // slot 0 has no slot before it in its block
+        if constexpr (PROPS) {  // ... when its properties match slot s-1's (matchProperties)
+            const u64 same = simd::ballot(w.props == simd::row_shr1(w.props));
+            for (u64 c = join & ~same; c; c &= c - 1) {
+                const u32 l = (u32)__builtin_ctzll(c);
+                if (!match_props(simd::readlane(w.props, l - 1), simd::readlane(w.props, l))) join &= ~(1ull << l);
+            }
+        }
+        serial = (join & simd::ballot(w.len > (u32)GRANULARITY)) != 0;
+        chg = drop | join;
+        const u64 keep = act & ~chg;
+        nkeep = (u32)__builtin_popcountll(keep);
+        const V rk = simd::rank_below(keep);
+        dst = (simd::sel(simd::ballot_mask(keep), rk, (L() - rk) + nkeep) + nBefore) & 63u;
+        nlen = w.len;
+        ntoff = w.toff;
+        ncap = w.cap;
+        jdst = jlen = simd::splat(0);
+        u64 heads = st & ~join & (join >> 1);
+        if (!heads) return;
+        const V ex = simd::scan_incl(w.len) - w.len;  // only differences inside one block are used
+        const u64 mCONT = simd::ballot(w.toff == simd::row_shr1(w.toff + w.len));
+        for (; heads; heads &= heads - 1) {  // sibling order, then head order: scour's order
+            const u32 lh = (u32)__builtin_ctzll(heads);                    // a head is never slot 7: lh <= 62
+            const u32 le = lh + (u32)__builtin_ctzll(~(join >> (lh + 1)));  // the run's last slot (same block)
+            const u64 rb = ((2ull << le) - 1ull) & ~((2ull << lh) - 1ull);  // lanes lh+1..le
+            const u32 off = simd::readlane(w.toff, lh), cap = simd::readlane(w.cap, lh);
+            const u32 exh = simd::readlane(ex, lh);
+            const u32 total = simd::readlane(ex, le) + simd::readlane(w.len, le) - exh;
+            u32 noff = off, nc = cap;
+            u64 cbits = 0;
+            if ((mCONT & rb) == rb) {  // the run's text is one contiguous range already
+                if (off & ARENA_BIT) nc = simd::readlane(w.toff, le) + simd::readlane(w.cap, le) - off;
+            } else if ((off & ARENA_BIT) && total <= cap) {  // append into the head's chunk
+                cbits = rb;
+            } else {  // a fresh chunk
+                nc = 2 * total < 32 ? 32u : 2 * total;
+                noff = top | ARENA_BIT;
+                top += nc;
+                need += nc;
+                cbits = rb | (1ull << lh);
+            }
+            if (cbits) {
+                const B cp = simd::ballot_mask(cbits);
+                jdst = simd::sel(cp, ex + (noff - exh), jdst);
+                jlen = simd::sel(cp, w.len, jlen);
+            }
+            nlen = simd::writelane(nlen, lh, total);
+            ntoff = simd::writelane(ntoff, lh, noff);
+            ncap = simd::writelane(ncap, lh, nc);
+        }
+    }
+    // Pack the m children [k0, k0 + m) of level-1 node pi; k is the popped block among them (already
+    // scoured once and stored: it is decided like the rest, and joins across a tombstone that pass dropped).
+    // false: nothing was done, and the pack needs the sibling loop -- a joining slot is longer than
+    // GRANULARITY (scour_serial), or the fresh chunks do not fit the arena (arena_gc).
+    SD bool pack_fused(u32 pi, u32 m, u32 k0, u32 k) {
+        RG_PROF(RP_PACK_FUSED);
+        const u32 r0 = k0 >> 3, r1 = (k0 + m - 1) >> 3, g0 = k0 & 7u;
+        const bool two = r1 != r0;
+        const u32 mA = two ? 8u - g0 : m;  // siblings in row r0; two rows: 1..7 in each
+        const Row a = rows.row(r0);
+        Row b;
+        if (two) b = rows.ldrow(r1);
+        V lenA, toffA, capA, jdA, jlA, dstA, lenB, toffB, capB, jdB, jlB, dstB;
+        u32 top = arenaTop, need = 0, nA, nB = 0;
+        u64 chgA, chgB = 0;
+        bool serA, serB = false;
+        pack_row(a, (mA == 8 ? ~0ull : (1ull << (mA * 8)) - 1ull) << (g0 * 8), 0, lenA, toffA, capA, jdA, jlA, dstA, nA, chgA, serA,
+                 top, need);
+        if (two) pack_row(b, (1ull << ((m - mA) * 8)) - 1ull, nA, lenB, toffB, capB, jdB, jlB, dstB, nB, chgB, serB, top, need);
+        if (serA | serB) {
+            RG_STAT(RS_PACK_FUSED_FB_SERIAL, 1);
+            return false;
+        }
+        if (arenaTop + need > arena_cap) {
+            RG_STAT(RS_PACK_FUSED_FB_GC, 1);
+            return false;
+        }
+        RG_STAT(RS_PACK_FUSED, 1);
+        RG_COUNT(RP_N_SCOUR, m);
+        RG_COUNT(RP_N_SCOUR_CHANGED, changed_blocks(chgA) + changed_blocks(chgB));
+#if defined(MTE_CPU) && defined(MTE_CPU_STATS)
+        for (u32 idx = 0; idx < m; idx++) {  // the sibling loop's counters: siblings decided / unchanged / changed
+            const u32 blk = k0 + idx;
+            RG_STAT(RS_SCOUR, 1);
+            RG_STAT(RS_PACK_SCOUR, 1);
+            if (!group_bits((blk >> 3) == r0 ? chgA : chgB, blk)) {
+                RG_STAT(RS_SCOUR_NOP, 1);
+                RG_STAT(RS_PACK_SCOUR_NOP, 1);
+            } else {
+                RG_STAT(blk == k ? RS_PACK_SELF_CHANGED : RS_PACK_SIB_CHANGED, 1);
+            }
+        }
+#endif
+        arenaTop = top;
+        if (chgA | chgB) {
+            // One fence for all copies, then one gather per row. No copy reads what another one writes:
+            // every destination is a fresh chunk above the old arenaTop or the free tail [off + len,
+            // off + cap) of a head's own chunk, and every source is text some slot held before this pack
+            // (chunks are never shared: split_at divides a chunk's capacity between the two pieces).
+            fence_arena();
+            if (chgA) RG_DUO(w |= 1ull << r0);
+            if (chgB) RG_DUO(w |= 1ull << r1);
+            copy_runs(jdA, a.toff, jlA);
+            if (two) copy_runs(jdB, b.toff, jlB);
+        }
+        u32 kk, base, extra;
+        if (!pack_plan(m, nA + nB, kk, base, extra)) return true;
+        // item t of the concatenated children is the t-th kept slot: each kept lane is pushed to its rank
+        Row t;
+        if (two) {
+            const B fromA = L() < nA;
+            auto gather = [&](const V& x0, const V& x1) MTE_LI { return simd::sel(fromA, simd::push(x0, dstA), simd::push(x1, dstB)); };
+            t.len = gather(lenA, lenB);
+            t.seq = gather(a.seq, b.seq);
+            t.rseq = gather(a.rseq, b.rseq);
+            t.meta = gather(a.meta, b.meta);
+            t.toff = gather(toffA, toffB);
+            t.cap = gather(capA, capB);
+            t.rm = gather(a.rm, b.rm);
+            t.sid = gather(a.sid, b.sid);
+            if constexpr (PROPS) t.props = gather(a.props, b.props);
+            if constexpr (WIDE) t.rm2 = gather(a.rm2, b.rm2);
+        } else {
+            t.len = simd::push(lenA, dstA);
+            t.seq = simd::push(a.seq, dstA);
+            t.rseq = simd::push(a.rseq, dstA);
+            t.meta = simd::push(a.meta, dstA);
+            t.toff = simd::push(toffA, dstA);
+            t.cap = simd::push(capA, dstA);
+            t.rm = simd::push(a.rm, dstA);
+            t.sid = simd::push(a.sid, dstA);
+            if constexpr (PROPS) t.props = simd::push(a.props, dstA);
+            if constexpr (WIDE) t.rm2 = simd::push(a.rm2, dstA);
+        }
+        t.meta = t.meta & ~NS_MASK;  // packed blocks: needsScour undefined
+        pack_place(pi, m, k0, kk, base, extra, t);
+        return true;
+    }
+    // blocks (aligned 8-lane groups) with a bit set in m
+    SD static u32 changed_blocks(u64 m) {
+        m |= m >> 4;
+        m |= m >> 2;
+        m |= m >> 1;
+        return (u32)__builtin_popcountll(m & 0x0101010101010101ull);
+    }
     // pack on an interior level: node pi of level lv underflowed; the children of its parent are
     // redistributed into max(1, min(7, T/4)) nodes, T their total child count.
     SD void pack_internal(u32 pi, u32 lv) {
@@ -1508,6 +1743,9 @@ struct RegEngine {
             // The popped block k is among them and is scoured a second time, as scourNode is in the
             // reference: a tombstone the first pass dropped had reset the merge chain, and the settled
             // text on its two sides, adjacent now, joins in this pass (RS_PACK_SELF_CHANGED counts it).
+            if constexpr (kFusedPack) {
+                if (pack_fused(pi, m, k0, k)) continue;  // (else: the serial walk or arena_gc, below)
+            }
             {
                 RG_PROF(RP_PACK_SIBS);
                 for (u32 idx = 0; idx < m; idx++) {
@@ -2024,7 +2262,7 @@ struct RegEngine {
                                               PF_RANGE, PF_ZAMBONI, PF_SCOUR, PF_HEAP, PF_FIND_SEG, PF_PACK,
                                               PF_LRU, PF_OPS, PN_RESOLVE, PN_SCOUR, PN_SCOUR_CHANGED, PN_PACK,
                                               PN_POP, PN_SPLIT_BLK, PN_DIRTY, PF_ALLOC, PF_OP_INS, PF_OP_REM,
-                                              PF_ZAM_MSN, PF_ZAM_EDIT, PF_SCOUR_CHAIN};
+                                              PF_ZAM_MSN, PF_ZAM_EDIT, PF_SCOUR_CHAIN, PF_SCOUR_WRITE};
             u64* o2 = p.prof + (u64)doc * PROF_SLOTS;
             for (u32 i = 0; i < RP_N; i++) o2[map[i]] += pf[i];
         }

@@ -7,7 +7,9 @@ set -e
 cd "$(dirname "$0")/../fluidframework_amd/csrc"
 B=../_build
 declare -A S=([apply]=2 [resolve]=3 [insert_slot]=4 [split]=5 [range]=6 [zamboni]=7 [scour]=8 [heap]=9 \
-              [find_seg]=10 [pack]=11 [lru]=12 [split_at]=21 [op_ins]=22 [op_rem]=23 [zam_msn]=24 [zam_edit]=25 [pack_sibs]=26)
+              [find_seg]=10 [pack]=11 [lru]=12 [split_at]=21 [op_ins]=22 [op_rem]=23 [zam_msn]=24 [zam_edit]=25 [pack_sibs]=26 [pack_fused]=27)
+# (pack_fused, the fused pack, stands against pack_sibs + pack of a build without it; lone_doc.py reports
+# them as scour_write, scour_chain and pack)
 build() {
   # mte_solo.o alone into rp_<name>, the prof build's other objects, the Makefile's link rule
   rm -f $B/rp_$1/mte_solo.o

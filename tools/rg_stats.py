@@ -30,7 +30,10 @@ NAMES = ["ops", "resolve", "res_rows", "res_nrows", "pop", "pop_big", "pop_heap"
          "pack_self_changed", "pack_sib_changed", "pack_one_row", "pack_two_rows", "pack_serial", "pack_gc",
          "pack_cascade", "pack_m8", "pack_grows", "pack_m_sum", "pack_kk_sum",
          # needsScour marks: as a second write of the row the edit has just written / folded into that write
-         "lru_rewrite", "lru_folded"]
+         "lru_rewrite", "lru_folded",
+         # packs the fused path took (pack_fused: all siblings decided at once, kept slots gathered by mask),
+         # and the ones it handed back to the sibling loop: a sibling on the serial walk, an arena_gc needed
+         "pack_fused", "pack_fused_fb_serial", "pack_fused_fb_gc"]
 
 
 def main():
@@ -73,6 +76,9 @@ def main():
         "pack_cascade_share": round(st["pack_cascade"] / max(st["pack"], 1), 4),
         "pack_siblings_mean": round(st["pack_m_sum"] / max(st["pack"], 1), 3),
         "pack_blocks_out_mean": round(st["pack_kk_sum"] / max(st["pack"], 1), 3),
+        # the fused pack: packs it took, and the share it handed back to the sibling loop
+        "pack_fused_share": round(st["pack_fused"] / max(st["pack"], 1), 6),
+        "pack_fused_fallback_share": round((st["pack_fused_fb_serial"] + st["pack_fused_fb_gc"]) / max(st["pack"], 1), 6),
         # a settle half on a second wave: of the ops after one whose settle pops, the
         # share whose first resolve would have to be repeated, and the rows a popping settle rewrites
         "duo_redo_share": round(st["duo_spec_redo"] / max(st["duo_spec_ok"] + st["duo_spec_redo"], 1), 4),
