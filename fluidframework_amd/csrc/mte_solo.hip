@@ -145,6 +145,12 @@ __global__ __launch_bounds__(64 * SOLO_WAVES) __attribute__((amdgpu_waves_per_eu
 #endif
 }
 
+#ifdef MTE_SOLO_LEAN_ONLY
+// code inspection only (make asm-solo EXTRA=-DMTE_SOLO_LEAN_ONLY): the critical kernel and nothing else
+template __global__ void k_solo<false, 0, false>(Params);
+}  // namespace mte
+#else
+
 // Bulk lean documents on the row engine (reg_engine.hpp): RW single-SIMD waves per CU (4, 8 = two per
 // SIMD, or 12), each with its SIMD's register file (or a half / third of it), replay one document
 // after another from the LPT queue. At 4 waves each wave owns a fixed quarter of the CU's LDS, 20
@@ -429,3 +435,4 @@ hipError_t launch_solo(const Params& p, bool gen, int full, u32 n_solo, bool ck,
 }
 
 }  // namespace mte
+#endif  // MTE_SOLO_LEAN_ONLY

@@ -127,7 +127,15 @@ enum RgStat : u32 {
     RS_LRU_REWRITE, RS_LRU_FOLDED,
     // packs taken by pack_fused, and the ones it handed back before any side effect: a joining slot longer
     // than GRANULARITY (the serial walk), fresh chunks that do not fit the arena (arena_gc)
-    RS_PACK_FUSED, RS_PACK_FUSED_FB_SERIAL, RS_PACK_FUSED_FB_GC, RS_N
+    RS_PACK_FUSED, RS_PACK_FUSED_FB_SERIAL, RS_PACK_FUSED_FB_GC,
+    // The places round 13 looked at (tests/test_reg_state_regs_cpu.py; kHeapInPlace and kMulDiv change the heap
+    // writes and the packs' divisions, the others count code that stayed as it was): resolves of documents
+    // of three or more rows that hit in their first / second row buffer; block splits whose new block starts
+    // the next row; heap entries written to register 1 (positions 64..127) and to registers 2..7; pops on the
+    // serial sift; packs by kk (RS_PACK_KK1 + kk - 1) and the ones with T % kk != 0; pack_internal rounds;
+    // ops room() refused
+    RS_HIT_FIRST, RS_HIT_SECOND, RS_SPLIT_NEXT_ROW, RS_HEAP_REG1, RS_HEAP_REG2, RS_SIFT_SERIAL, RS_PACK_KK1, RS_PACK_KK2,
+    RS_PACK_KK3, RS_PACK_KK4, RS_PACK_KK5, RS_PACK_KK6, RS_PACK_KK7, RS_PACK_REM, RS_PACK_INTERNAL, RS_ROOM_REFUSED, RS_N
 };
 inline u64 g_rg_stats[RS_N + 64];
 #define RG_STAT(i, n) (g_rg_stats[i] += (u64)(n))
@@ -170,6 +178,12 @@ inline RgDuoStat g_rg_duo;
 
 #ifndef MTE_FUSED_PACK
 #define MTE_FUSED_PACK 1  // RegEngine::kFusedPack
+#endif
+// The parts of round 13, one bit each: 1 RegEngine::kHeapInPlace, 4 RegEngine::kMulDiv.
+// 0 builds neither: the A/B twin. (Bit 2 was resolve's hit taken from the buffer that hit, 8 one exit
+// from the replay loop, 16 the loop's state re-homed at the head of each op: measured slower, removed.)
+#ifndef MTE_STATE_REGS
+#define MTE_STATE_REGS 5
 #endif
 
 struct RSeg {
@@ -214,6 +228,14 @@ struct RegEngine {
     // engines; elsewhere zamboni keeps the sibling loop of scours and pack_leaves.
     // (MTE_FUSED_PACK=0 / 2 builds it into no / every engine: the unfused twin of the CPU suite, A/B libraries.)
     static constexpr bool kFusedPack = MTE_FUSED_PACK == 2 || (MTE_FUSED_PACK == 1 && !PAGED && NR == (int)RG_ROWS);
+    // Round 13, on the lean engines among those, so that every k_rows kernel and the PROPS /
+    // WIDE k_solo kernels (not timed with these parts) stay the code they were: a heap entry is written by
+    // a lane compare in each register it can be in, not by a branch per register (kHeapInPlace: the
+    // sixteen heap registers have one home across a push and a pop); a pack's T / kk is a multiply and a
+    // shift (kMulDiv).
+    static constexpr bool kOwnRows = !PAGED && NR == (int)RG_ROWS && !PROPS && !WIDE;
+    static constexpr bool kHeapInPlace = kOwnRows && (MTE_STATE_REGS & 1) != 0;
+    static constexpr bool kMulDiv = kOwnRows && (MTE_STATE_REGS & 4) != 0;
     static constexpr u32 MAXC = WIDE ? 64u : 32u;  // client ids below this (rm, rm2)
     typedef simd::V V;
     typedef simd::B B;
@@ -587,6 +609,9 @@ struct RegEngine {
             RG_DUO(resolved(false, 0));
             return f;
         }
+        RG_STAT(inb ? RS_HIT_SECOND : RS_HIT_FIRST, nrows >= 3);
+        // (hit_row called on the buffer that hit, with no copy of b onto a, measured 2 % slower: the code of
+        // hit_row twice, 34 instructions more per op)
         if (inb) a = b;
         hit_row(a, r, hit, v, incl);
         RG_DUO(resolved(true, f.row));
@@ -716,6 +741,7 @@ struct RegEngine {
         if (!ensure_blocks(n_lb + 1)) return;
         shift_blocks(k + 1, 1);
         const u32 r = k >> 3, r2 = (k + 1) >> 3;
+        RG_STAT(RS_SPLIT_NEXT_ROW, r2 != r);
         const V sl = L() & 7u;
         const B lo = in_group(k + 1) & (sl < 4u), hi2 = in_group(k + 1) & (sl >= 4u), hi = in_group(k) & (sl >= 4u);
         const V src = (L() + (r2 == r ? 0u : 64u) - 4u) & 63u;  // new slot s <- old slot 4+s of block k
@@ -780,8 +806,20 @@ struct RegEngine {
     }
     template <int D>
     SD static void hwr(HeapRegs& A, u32 q, u32 v) {
-        const u32 l = q & 63u;
-        if constexpr (D <= 5) {
+        [[maybe_unused]] const u32 l = q & 63u;  // (the lane compares below take q itself)
+        if constexpr (kHeapInPlace && D >= 7) {
+            // no branch picks the register: each is rewritten where it lives, by a lane compare that holds in
+            // the one register of position q (q - 64 * i names no lane elsewhere: it wraps or is >= 64)
+            if constexpr (D == 7) {
+                A.x2 = simd::sel(L() == q - 128u, v, A.x2);
+                A.x3 = simd::sel(L() == q - 192u, v, A.x3);
+            } else {
+                A.x4 = simd::sel(L() == q - 256u, v, A.x4);
+                A.x5 = simd::sel(L() == q - 320u, v, A.x5);
+                A.x6 = simd::sel(L() == q - 384u, v, A.x6);
+                A.x7 = simd::sel(L() == q - 448u, v, A.x7);
+            }
+        } else if constexpr (D <= 5) {
             A.set(0, simd::writelane(A.get(0), l, v));
         } else if constexpr (D == 6) {
             A.set(1, simd::writelane(A.get(1), l, v));
@@ -807,6 +845,27 @@ struct RegEngine {
         return d <= 5 ? hrd<0>(HS, q) : d == 6 ? hrd<6>(HS, q) : d == 7 ? hrd<7>(HS, q) : hrd<8>(HS, q);
     }
     SD void hset(u32 q, u32 sid, u32 key) {
+        if constexpr (kHeapInPlace) {
+            // registers 0 and 1 by a lane compare, both every time: no branch picks the register, so the
+            // sixteen heap registers have one home across a push (q >= 128: q - 64 names no lane; q < 64
+            // neither: it wraps)
+            const B a0 = L() == q, a1 = L() == q - 64u;
+            HK.r0 = simd::sel(a0, key, HK.r0);
+            HS.r0 = simd::sel(a0, sid, HS.r0);
+            HK.r1 = simd::sel(a1, key, HK.r1);
+            HS.r1 = simd::sel(a1, sid, HS.r1);
+            RG_STAT(RS_HEAP_REG1, q >= 64u && q < 128u);
+            if (q >= 128u) {  // one plain branch, its body straight-line
+                RG_STAT(RS_HEAP_REG2, 1);
+                hwr<7>(HK, q, key);
+                hwr<7>(HS, q, sid);
+                hwr<8>(HK, q, key);
+                hwr<8>(HS, q, sid);
+            }
+            return;
+        }
+        RG_STAT(RS_HEAP_REG1, q >= 64u && q < 128u);
+        RG_STAT(RS_HEAP_REG2, q >= 128u);
         const u32 d = hlevel(q);
         if (d <= 5) {
             hwr<0>(HK, q, key);
@@ -916,6 +975,14 @@ struct RegEngine {
         const B mv = simd::ballot_mask(path);
         V N0 = simd::sel(mv, kc, K0), T0 = simd::sel(mv, sc, S0);
         if (path & 2u) newTop = (i32)simd::readlane(kc, 1);
+        if constexpr (kHeapInPlace) {  // (as hset: k < 128 here)
+            const B a0 = L() == k, a1 = L() == k - 64u;
+            HK.r0 = simd::sel(a0, lk, N0);
+            HS.r0 = simd::sel(a0, ls, T0);
+            HK.r1 = simd::sel(a1, lk, K1);
+            HS.r1 = simd::sel(a1, ls, S1);
+            return;
+        }
         if (k < 64u) {
             N0 = simd::writelane(N0, k, lk);
             T0 = simd::writelane(T0, k, ls);
@@ -948,7 +1015,10 @@ struct RegEngine {
         i32 newTop = (i32)lk;
         if (m >= 1) {
             if (m < 128u) pop_fast(m, lk, ls, newTop);
-            else sift<0>(1, m, lk, ls, newTop);
+            else {
+                RG_STAT(RS_SIFT_SERIAL, 1);
+                sift<0>(1, m, lk, ls, newTop);
+            }
         }
         heapTop = newTop;
         heapSize = m;
@@ -1379,6 +1449,26 @@ struct RegEngine {
         adirty = true;
     }
 
+    // T / kk and T % kk of a pack: kk in 1..7, T <= 64. The hardware has no integer divide (a run-time one is
+    // some 25 vector instructions through a float reciprocal), so with kMulDiv the quotient is
+    // (T * ceil(512 / kk)) >> 9, exact for these ranges (T * (kk * ceil(512 / kk) - 512) < 512); the seven
+    // multipliers, less one, are nine bits each of one constant.
+    SD static void div_mul(u32 T, u32 kk, u32& q, u32& r) {
+        constexpr u64 M = 511ull | (255ull << 9) | (170ull << 18) | (127ull << 27) | (102ull << 36) | (85ull << 45) | (73ull << 54);
+        const u32 mul = ((u32)(M >> (9u * (kk - 1u))) & 511u) + 1u;
+        q = (T * mul) >> 9;
+        r = T - q * kk;
+    }
+    SD static void div_small(u32 T, u32 kk, u32& q, u32& r) {
+        RG_STAT(RS_PACK_KK1 + (kk - 1u), 1);
+        RG_STAT(RS_PACK_REM, T % kk != 0);
+        if constexpr (kMulDiv) {
+            div_mul(T, kk, q, r);
+        } else {
+            q = T / kk;
+            r = T % kk;
+        }
+    }
     // pack (mergeTree.ts:1368-1420), leaf level: the m children [k0, k0+m) of level-1 node pi
     // (already re-scoured; lane i of cn = child i's count) become max(1, min(7, T/4)) fresh blocks.
     SD void pack_leaves(u32 pi, u32 m, u32 k0, V cn) {
@@ -1390,7 +1480,8 @@ struct RegEngine {
         u32 kk = T / 4;
         if (kk > 7) kk = 7;
         if (kk < 1) kk = 1;
-        const u32 base = T / kk, extra = T % kk;
+        u32 base, extra;
+        div_small(T, kk, base, extra);
         RG_STAT(RS_PACK_KK_SUM, kk);
         RG_STAT(RS_PACK_GROWS, kk > m);
         RG_STAT(RS_PACK_CASCADE, kk < 4 && height > 2);
@@ -1466,8 +1557,7 @@ struct RegEngine {
         kk = T / 4;
         if (kk > 7) kk = 7;
         if (kk < 1) kk = 1;
-        base = T / kk;
-        extra = T % kk;
+        div_small(T, kk, base, extra);
         RG_STAT(RS_PACK_KK_SUM, kk);
         RG_STAT(RS_PACK_GROWS, kk > m);
         RG_STAT(RS_PACK_CASCADE, kk < 4 && height > 2);
@@ -1690,7 +1780,9 @@ struct RegEngine {
             u32 kk = T / 4;
             if (kk > 7) kk = 7;
             if (kk < 1) kk = 1;
-            const u32 base = T / kk, extra = T % kk;
+            u32 base, extra;
+            div_small(T, kk, base, extra);
+            RG_STAT(RS_PACK_INTERNAL, 1);
             const i32 d = (i32)kk - (i32)m;
             // lanes after the old range move by d
             const V src = L() - (u32)d;
@@ -2020,7 +2112,10 @@ struct RegEngine {
         // runs the EXT kernels, so here the flag is ignored like the lean LDS kernels do)
         if ((op.flags & (MTE_F_REL | MTE_F_PERM)) || (!PROPS && op.props)) return false;
         if (type != MTE_OP_NOOP && (op.client == 0 || op.client >= MAXC)) return false;
-        if (!room()) return false;
+        if (!room()) {
+            RG_STAT(RS_ROOM_REFUSED, 1);
+            return false;
+        }
         const u32 C = op.client;
         const i32 seq = op.seq, R = op.ref_seq;
         if (type != MTE_OP_NOOP && !(curSeq < seq)) {

@@ -33,7 +33,13 @@ NAMES = ["ops", "resolve", "res_rows", "res_nrows", "pop", "pop_big", "pop_heap"
          "lru_rewrite", "lru_folded",
          # packs the fused path took (pack_fused: all siblings decided at once, kept slots gathered by mask),
          # and the ones it handed back to the sibling loop: a sibling on the serial walk, an arena_gc needed
-         "pack_fused", "pack_fused_fb_serial", "pack_fused_fb_gc"]
+         "pack_fused", "pack_fused_fb_serial", "pack_fused_fb_gc",
+         # the places round 13 restated (tests/test_reg_state_regs_cpu.py): resolves of documents of three or
+         # more rows hitting in their first / second row buffer; block splits whose new block starts the next
+         # row; heap entries written to register 1 / to registers 2..7; pops on the serial sift; packs by kk,
+         # packs with T % kk != 0 (pack_internal's rounds count in both); pack_internal rounds; ops room() refused
+         "hit_first", "hit_second", "split_next_row", "heap_reg1", "heap_reg2", "sift_serial", "pack_kk1", "pack_kk2",
+         "pack_kk3", "pack_kk4", "pack_kk5", "pack_kk6", "pack_kk7", "pack_rem", "pack_internal", "room_refused"]
 
 
 def main():
