@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <list>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -19,6 +20,7 @@
 #include "ck_plan.hpp"
 #include "engine_types.hpp"
 #include "host_batch.hpp"
+#include "matrix.h"
 #include "view.h"
 
 #pragma GCC visibility push(hidden)
@@ -251,6 +253,21 @@ struct mte_engine {
     DevBuf<uint32_t> d_vpos, d_vtotals;
     DevBuf<uint16_t> d_vtext;
 
+    // ---- SharedMatrix reads (matrix.cpp): each queried matrix's cell table, built at its first query from
+    // the current replay results and kept until they go (mx_drop_tables: mte_load, mte_generate, mte_replay,
+    // mte_destroy); the plan's and the results' device buffers, grown as calls need them and kept
+    std::unordered_map<uint64_t, MxTable> mx_tabs;  // rows_doc << 32 | cols_doc -> its table, inside a slab
+    std::list<DevBuf<uint64_t>> mx_slabs;           // one per call that built tables
+    uint64_t mx_tables_built = 0;                   // running count (info key "mx_tables_built")
+    DevBuf<MxEntry> d_mx_ent;
+    DevBuf<MxGroup> d_mx_groups;
+    DevBuf<MxRange> d_mx_ranges;
+    DevBuf<MxRect> d_mx_rects;
+    DevBuf<MxQuery> d_mx_q;
+    DevBuf<MxResult> d_mx_out;
+    DevBuf<MxTable> d_mx_tables;
+    DevBuf<uint32_t> d_mx_pos, d_mx_ph, d_mx_totals, d_mx_handle, d_mx_vals, d_mx_flag;
+
     // ---- last load and last run
     bool replayed = false;
     std::vector<DocRes> res;
@@ -339,6 +356,11 @@ int fetch_out_row_map(mte_engine* e, uint64_t row, bool& has, uint32_t* w);
 int fetch_handle_table(mte_engine* e, uint32_t d, std::vector<uint32_t>& w);
 int fetch_cell_handles(mte_engine* e, std::vector<uint32_t>& h);
 int fetch_catch_up_records(mte_engine* e, uint32_t d, std::vector<uint4>& rec);
+
+// ---- matrix.cpp
+// Every SharedMatrix cell table goes: the results they were built from are about to change. (The caller
+// has made the engine's device current.)
+void mx_drop_tables(mte_engine* e);
 
 // ---- engine_ckpt.cpp: the device half of incremental replay (option retain; ck_plan.hpp is the other)
 int ck_match_batch(mte_engine* e, const mte_batch* b);  // mte_load: which documents continue

@@ -408,6 +408,7 @@ void mte_destroy(mte_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    mx_drop_tables(e);
     for (int i = 0; i < 2; i++) {
         if (e->stage[i]) (void)hipHostFree(e->stage[i]);
         if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]);
@@ -517,6 +518,7 @@ static int load_cells(mte_engine* e, const mte_batch* b, const std::vector<uint3
 int mte_load(mte_engine* e, const mte_batch* b) {
     if (!e || !b) return MTE_E_ARG;
     HIP_TRY(e, hipSetDevice(e->device));
+    mx_drop_tables(e);
     copy_batch(e->hb, b, false);
     e->emit_tables = false;
     e->generated = false;
@@ -686,6 +688,7 @@ int mte_generate_ids(mte_engine* e, uint32_t kind, uint32_t n_docs, uint32_t n_o
     e->map_words = MAP_WORDS;  // the generator's property sets hold at most four keys
     if (kind != 2 && kind != 3 && kind != 5) return set_err(e, MTE_E_ARG, "generator kind must be 2, 3 or 5");
     HIP_TRY(e, hipSetDevice(e->device));
+    mx_drop_tables(e);
     e->ck.reset();  // (a new batch: no checkpoint of the last one may be continued)
     e->P.cell_mode = 0;
     e->hb = HostBatch();

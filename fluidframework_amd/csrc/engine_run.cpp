@@ -577,6 +577,8 @@ int mte_retain(mte_engine* e, int on) { return e ? mte_set_option(e, "retain", o
 int mte_replay(mte_engine* e, mte_stats* out) {
     if (!e) return MTE_E_ARG;
     if (!e->P.ops) return set_err(e, MTE_E_STATE, "mte_replay before mte_load/mte_generate");
+    HIP_TRY(e, hipSetDevice(e->device));
+    mx_drop_tables(e);  // (SharedMatrix cell tables of the last pass's results)
     int rc;
     if (e->n_cells && !e->generated) {
         // cell ops: pass 1 evaluates adjustPosition in both vectors of every cell op, pass 2 replays

@@ -109,6 +109,16 @@ MTE_VIEW_OK, MTE_VIEW_PAST_END, MTE_VIEW_OUT_OF_WINDOW, MTE_VIEW_DOC_FAILED, MTE
 MTE_VIEW_NO_CLIENT = 0xFFFFFFFF
 MTE_VIEW_F_REMOVED = 1
 
+# SharedMatrix reads (mte_matrix_cells): the query and result records, and their constants.
+CELL_Q_DTYPE = np.dtype([("rows_doc", "<u4"), ("cols_doc", "<u4"), ("kind", "<u4"), ("row", "<u4"), ("col", "<u4"),
+                         ("n_rows", "<u4"), ("n_cols", "<u4"), ("pad", "<u4")])
+CELL_R_DTYPE = np.dtype([("status", "<i4"), ("row_count", "<u4"), ("col_count", "<u4"), ("value", "<u4"),
+                         ("row_handle", "<u4"), ("col_handle", "<u4"), ("val_off", "<u8")])
+assert CELL_Q_DTYPE.itemsize == 32 and CELL_R_DTYPE.itemsize == 32
+MTE_MQ_SHAPE, MTE_MQ_CELL, MTE_MQ_RECT = 0, 1, 2
+MTE_MX_OK, MTE_MX_OUT_OF_RANGE, MTE_MX_DOC_FAILED, MTE_MX_BAD_QUERY = 0, 1, 2, 3
+MTE_CELL_NONE = 0xFFFFFFFF
+
 # Every symbol declared in include/mte.h (checked by tests/test_abi.py).
 EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mte_last_error", "mte_load",
            "mte_replay", "mte_generate", "mte_generate_ids", "mte_export_batch", "mte_doc_status", "mte_text", "mte_length", "mte_segments",
@@ -117,6 +127,7 @@ EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mt
            "mte_builder_add_matrix_log", "mte_builder_add_matrix_from_summary", "mte_snapshot_matrix",
            "mte_builder_batch", "mte_builder_open_doc", "mte_builder_append_messages", "mte_retain",
            "mte_builder_open_doc_from_summary", "mte_views", "mte_client_slot", "mte_view_props",
+           "mte_matrix_cells", "mte_value_text",
            "mte_builder_error", "mte_builder_destroy"]
 
 _lib = None
@@ -188,6 +199,9 @@ def lib():
             L.mte_views.argtypes = [vp, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
             L.mte_client_slot.argtypes = [vp, u32, ctypes.c_char_p, ctypes.POINTER(u32)]
             L.mte_view_props.argtypes = [vp, u32, u32, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
+        if hasattr(L, "mte_matrix_cells"):  # (A/B runs load older experiment builds)
+            L.mte_matrix_cells.argtypes = [vp, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
+            L.mte_value_text.argtypes = [vp, u32, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
         L.mte_builder_error.argtypes = [vp]
         L.mte_builder_error.restype = ctypes.c_char_p
         L.mte_builder_destroy.argtypes = [vp]
@@ -424,6 +438,33 @@ class Engine:
         self._check(lib().mte_view_props(self._h, doc, row, buf, n.value + 1, ctypes.byref(n)), "mte_view_props")
         return json.loads(buf.raw[: n.value].decode("utf-8"))
 
+    def matrix_cells(self, queries):
+        """mte_matrix_cells: IMatrixReader reads (rowCount / colCount, getCell, dense ranges) of the
+        replayed matrices, on the GPU, without the summary blob or the whole-batch download. queries: a
+        CELL_Q_DTYPE array, or an iterable of (rows_doc, cols_doc, kind, row, col, n_rows, n_cols).
+        Returns (results: CELL_R_DTYPE array in query order, vals: uint32 array of the RECT queries'
+        value ids; RECT i's ids are vals[val_off : val_off + n_rows * n_cols], row-major)."""
+        if not (isinstance(queries, np.ndarray) and queries.dtype == CELL_Q_DTYPE):
+            queries = np.array([tuple(int(x) for x in t) + (0,) * (8 - len(t)) for t in queries], dtype=CELL_Q_DTYPE)
+        q = np.ascontiguousarray(queries)
+        out = np.zeros(len(q), dtype=CELL_R_DTYPE)
+        n = ctypes.c_size_t()
+        fn = lib().mte_matrix_cells
+        self._check(fn(self._h, q.ctypes.data, len(q), out.ctypes.data, None, 0, ctypes.byref(n)), "mte_matrix_cells")
+        vals = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self._check(fn(self._h, q.ctypes.data, len(q), out.ctypes.data, vals.ctypes.data, n.value, ctypes.byref(n)),
+                        "mte_matrix_cells")
+        return out, vals
+
+    def value_text(self, value_id):
+        """The canonical JSON text of a value id of the loaded batch (0: "null")."""
+        n = ctypes.c_size_t()
+        self._check(lib().mte_value_text(self._h, value_id, None, 0, ctypes.byref(n)), "mte_value_text")
+        buf = ctypes.create_string_buffer(n.value + 1)
+        self._check(lib().mte_value_text(self._h, value_id, buf, n.value + 1, ctypes.byref(n)), "mte_value_text")
+        return buf.raw[: n.value].decode("utf-8")
+
     def _str_call(self, fn, doc, *extra):
         n = ctypes.c_size_t()
         self._check(fn(self._h, doc, None, 0, ctypes.byref(n), *extra), fn.__name__)
@@ -540,6 +581,57 @@ class Engine:
         out = np.zeros(nw * 64 * 5, dtype=np.uint32)
         self._check(lib().mte_wave_selftest(self._h, values.ctypes.data, out.ctypes.data, nw), "mte_wave_selftest")
         return out.reshape(nw, 5, 64)
+
+
+class SharedMatrixReader:
+    """IMatrixReader (matrix.ts:147-171) of one replayed matrix: a (rows_doc, cols_doc) pair of an Engine
+    that has replayed. Every read is one mte_matrix_cells call; values come back parsed (None for
+    undefined and for null, which the summary cannot tell apart either)."""
+
+    def __init__(self, engine, rows_doc, cols_doc):
+        self.e, self.rows_doc, self.cols_doc = engine, rows_doc, cols_doc
+        self._texts = {}
+
+    def _value(self, vid):
+        vid = int(vid)
+        if vid == MTE_CELL_NONE:
+            return None
+        if vid not in self._texts:
+            self._texts[vid] = json.loads(self.e.value_text(vid))
+        return self._texts[vid]
+
+    def _one(self, kind, row=0, col=0, n_rows=0, n_cols=0):
+        out, vals = self.e.matrix_cells([(self.rows_doc, self.cols_doc, kind, row, col, n_rows, n_cols)])
+        r = out[0]
+        if r["status"] == MTE_MX_OUT_OF_RANGE:
+            raise IndexError(f"({row}, {col}) + ({n_rows}, {n_cols}) outside {r['row_count']} x {r['col_count']}")
+        if r["status"] != MTE_MX_OK:
+            raise MteError(f"matrix ({self.rows_doc}, {self.cols_doc}): query status {int(r['status'])}")
+        return r, vals
+
+    @property
+    def rowCount(self):  # noqa: N802 (reference name)
+        return int(self._one(MTE_MQ_SHAPE)[0]["row_count"])
+
+    @property
+    def colCount(self):  # noqa: N802
+        return int(self._one(MTE_MQ_SHAPE)[0]["col_count"])
+
+    def getCell(self, row, col):  # noqa: N802
+        return self._value(self._one(MTE_MQ_CELL, row, col)[0]["value"])
+
+    def toArray(self, r0=0, c0=0, n_rows=None, n_cols=None):  # noqa: N802
+        """The n_rows x n_cols cells from (r0, c0) on (to the matrix's end by default) as a list of rows:
+        one RECT query."""
+        if n_rows is None or n_cols is None:
+            shape = self._one(MTE_MQ_SHAPE)[0]
+            n_rows = max(int(shape["row_count"]) - r0, 0) if n_rows is None else n_rows
+            n_cols = max(int(shape["col_count"]) - c0, 0) if n_cols is None else n_cols
+        r, vals = self._one(MTE_MQ_RECT, r0, c0, n_rows, n_cols)
+        o = int(r["val_off"])
+        ids = vals[o:o + n_rows * n_cols]
+        table = {int(v): self._value(v) for v in np.unique(ids)}
+        return [[table[int(v)] for v in ids[i * n_cols:(i + 1) * n_cols]] for i in range(n_rows)]
 
 
 class MergeTreeClient:

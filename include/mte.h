@@ -384,6 +384,60 @@ int mte_client_slot(mte_engine* e, uint32_t doc, const char* client_id, uint32_t
  * row's map record alone. buf may be NULL to query *len. */
 int mte_view_props(mte_engine* e, uint32_t doc, uint32_t row, char* buf, size_t cap, size_t* len);
 
+/* ---- SharedMatrix reads ------------------------------------------------------------------------
+ * IMatrixReader (matrix.ts:149-171) of the replayed matrices, answered on the GPU from what the pass
+ * left there (the vectors' output rows, the cell handles, the HandleTables), many matrices a call,
+ * without the summary blob and without the whole-batch download. A matrix is a (rows_doc, cols_doc) pair
+ * as in mte_snapshot_matrix; all reads are in the observer's (local) view. */
+#define MTE_CELL_NONE 0xFFFFFFFFu   /* getCell -> undefined: an unallocated row/col handle, or no cell stored */
+enum {
+    MTE_MQ_SHAPE = 0,  /* rowCount / colCount (matrix.ts:149-150) alone */
+    MTE_MQ_CELL = 1,   /* SharedMatrix.getCell(row, col) (matrix.ts:152-171): the two positions' handles
+                          (PermutationVector.getMaybeHandle, permutationvector.ts:170-174), then the cell
+                          stored under the pair (SparseArray2D.getCell, sparsearray2d.ts:66-84) */
+    MTE_MQ_RECT = 2,   /* the n_rows x n_cols getCells from (row, col) on, row-major */
+};
+enum {                         /* mte_cell_r.status; none of them fails the call */
+    MTE_MX_OK = 0,
+    MTE_MX_OUT_OF_RANGE = 1,   /* CELL: row >= row_count or col >= col_count (the reference asserts there,
+                                  permutationvector.ts:171, matrix.ts:167); RECT: the rectangle is not wholly inside the matrix, and
+                                  its ids are all MTE_CELL_NONE. A RECT with a zero side is OK and has no ids */
+    MTE_MX_DOC_FAILED = 2,     /* the replay status of rows_doc or cols_doc is not MTE_DOC_OK */
+    MTE_MX_BAD_QUERY = 3,      /* a document index out of range, an unknown kind, n_rows * n_cols above 2^31 */
+};
+typedef struct mte_cell_q {
+    uint32_t rows_doc, cols_doc;
+    uint32_t kind;             /* MTE_MQ_* */
+    uint32_t row, col;         /* CELL, RECT */
+    uint32_t n_rows, n_cols;   /* RECT */
+    uint32_t pad;
+} mte_cell_q;
+typedef struct mte_cell_r {    /* 32 bytes */
+    int32_t status;            /* MTE_MX_* */
+    uint32_t row_count, col_count; /* each vector's getLength() in the local view; every kind fills them
+                                      (0 with DOC_FAILED / BAD_QUERY) */
+    uint32_t value;            /* CELL: value id (index into the batch's val_text, mte_value_text; 0 = null),
+                                  or MTE_CELL_NONE: either handle is unallocated or no live cell is stored under
+                                  the pair. The summary blob cannot tell null from undefined (both print null);
+                                  here too value id 0 covers both, as MTE_OP_CELL says */
+    uint32_t row_handle, col_handle; /* CELL: PermutationVector.getMaybeHandle (0 = Handle.unallocated). A visible
+                                  row that is no permutation run (a text document passed by mistake) counts as
+                                  unallocated */
+    uint64_t val_off;          /* RECT: first of its n_rows * n_cols ids, row-major, in vals */
+} mte_cell_r;
+/* out[i] answers q[i]. A cell's value is the one mte_snapshot_matrix prints: the loaded cells first (a
+ * loaded cell is cleared when the replay freed its row or col handle at all), then every set both vectors
+ * defined, in log order, each overwriting its (row handle, col handle); a set is cleared when its row or
+ * col handle was freed after it (onRowHandlesRecycled / onColHandlesRecycled, matrix.ts:626-640).
+ * The RECT queries' ids go to vals (vals_cap ids; *vals_len = the ids they need): every RECT with status OK
+ * or OUT_OF_RANGE is laid out, in query order. vals may be NULL to size the buffer (out is still filled); a
+ * vals_cap too small is MTE_E_RANGE with *vals_len set. MTE_E_STATE before a replay. */
+int mte_matrix_cells(mte_engine* e, const mte_cell_q* q, size_t n, mte_cell_r* out, uint32_t* vals, size_t vals_cap,
+                     size_t* vals_len);
+/* The canonical JSON text of value id value_id of the loaded batch (what the summary blob prints for it;
+ * id 0 is null). buf may be NULL to query *len. MTE_E_RANGE for an id the batch does not have. */
+int mte_value_text(mte_engine* e, uint32_t value_id, char* buf, size_t cap, size_t* len);
+
 /* Multi-GPU: documents are sharded by id across ranks (one process per GPU) and the
  * only collective of the path is this all-gather of the per-document summary records, over RCCL
  * (xGMI inside a node). The communicator is RCCL's own: rank 0 makes an id (mte_rccl_unique_id),

@@ -21,6 +21,19 @@ export interface ViewQuery { doc: number; refSeq: number; client?: number; kind:
 export interface ViewResult { status: number; row: number; offset: number; length: number; curPos: number;
     removed: boolean; text?: string; }
 
+/** SharedMatrix reads (BatchedMergeEngine.matrixCells): what to read, and how each query ended. */
+export declare const MatrixQuery: { Shape: 0; Cell: 1; Rect: 2 };
+export declare const MatrixStatus: { Ok: 0; OutOfRange: 1; DocFailed: 2; BadQuery: 3 };
+/** One IMatrixReader read of the matrix whose rows / cols vectors are documents rowsDoc / colsDoc (a
+ *  { matrix } entry of load()). Cell: getCell(row, col). Rect: the nRows x nCols getCells from (row, col). */
+export interface MatrixCellQuery { rowsDoc: number; colsDoc: number; kind: 0 | 1 | 2; row?: number; col?: number;
+    nRows?: number; nCols?: number; }
+/** rowCount / colCount: every kind. Cell: value (undefined: no cell, or an unallocated row / col), rowHandle,
+ *  colHandle (0 = unallocated); status OutOfRange past either count. Rect: values, an array of nRows rows;
+ *  status OutOfRange (every value undefined) when the rectangle is not wholly inside the matrix. */
+export interface MatrixCellResult { status: number; rowCount: number; colCount: number; value?: unknown;
+    rowHandle?: number; colHandle?: number; values?: unknown[][]; }
+
 export interface ReplayStats { docs: number; ops: number; messages: number; failedDocs: number; kernelMs: number; }
 export interface DocSummary {
     checksum: bigint | string; ops: number; length: number; segments: number;
@@ -69,6 +82,11 @@ export declare class BatchedMergeEngine {
     clientSlot(doc: number, clientId: string): number;
     /** mte_view_props: the properties of segment table row `row` of a document, or null. */
     viewProps(doc: number, row: number): Record<string, unknown> | null;
+    /** mte_matrix_cells: rowCount / colCount, getCell and dense ranges of the replayed matrices, many matrices a
+     *  call, answered on the GPU without the summary blob. results[i] answers queries[i]. */
+    matrixCells(queries: MatrixCellQuery[]): MatrixCellResult[];
+    /** mte_value_text: the canonical JSON text of a value id of the loaded batch. */
+    valueText(id: number): string;
 }
 
 /** An RCCL communicator handle (released by rcclCommDestroy or when collected). */

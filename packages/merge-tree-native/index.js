@@ -16,6 +16,10 @@ const ViewKind = Object.freeze({ Length: 0, Locate: 1, Text: 2 });
 const ViewStatus = Object.freeze({ Ok: 0, PastEnd: 1, OutOfWindow: 2, DocFailed: 3, BadQuery: 4 });
 const VIEW_NO_CLIENT = 0xFFFFFFFF;
 const VIEW_F_REMOVED = 1;
+/** SharedMatrix reads (mte_matrix_cells): kinds, per-query statuses, the id of "no cell". */
+const MatrixQuery = Object.freeze({ Shape: 0, Cell: 1, Rect: 2 });
+const MatrixStatus = Object.freeze({ Ok: 0, OutOfRange: 1, DocFailed: 2, BadQuery: 3 });
+const CELL_NONE = 0xFFFFFFFF;
 
 class BatchedMergeEngine {
     constructor(options = {}) {
@@ -127,6 +131,51 @@ class BatchedMergeEngine {
     snapshotV1(doc) { this._idle(); return JSON.parse(addon.snapshotV1(this._engine, doc)); }
     /** SharedMatrix summary of a { matrix } document pair (its rows and cols PermutationVectors) */
     snapshotMatrix(rowsDoc, colsDoc) { this._idle(); return JSON.parse(addon.snapshotMatrix(this._engine, rowsDoc, colsDoc)); }
+    /**
+     * mte_matrix_cells: IMatrixReader reads (matrix.ts:147-171) of replayed { matrix } document pairs, answered
+     * on the GPU without the summary blob. queries: [{ rowsDoc, colsDoc, kind, row, col, nRows, nCols }].
+     * Returns, in query order, [{ status, rowCount, colCount, value?, rowHandle?, colHandle?, values? }]: Shape ->
+     * the counts alone; Cell -> value (getCell: the parsed JSON, undefined for no cell), rowHandle / colHandle
+     * (0 = unallocated); Rect -> values, the nRows x nCols getCells from (row, col) on as an array of rows (all
+     * undefined when status is OutOfRange).
+     */
+    matrixCells(queries) {
+        this._idle();
+        const qb = Buffer.alloc(queries.length * 32);
+        queries.forEach((q, i) => {
+            [q.rowsDoc, q.colsDoc, q.kind, q.row, q.col, q.nRows, q.nCols, 0].forEach((v, k) => {
+                qb.writeUInt32LE((v || 0) >>> 0, i * 32 + 4 * k);
+            });
+        });
+        const [rb, vb] = addon.matrixCells(this._engine, qb);
+        const texts = new Map();
+        const value = (id) => {
+            if (id === CELL_NONE) return undefined;
+            if (!texts.has(id)) texts.set(id, JSON.parse(addon.valueText(this._engine, id)));
+            return texts.get(id);
+        };
+        return queries.map((q, i) => {
+            const o = i * 32;
+            const r = { status: rb.readInt32LE(o), rowCount: rb.readUInt32LE(o + 4), colCount: rb.readUInt32LE(o + 8) };
+            if (q.kind === MatrixQuery.Cell && r.status === MatrixStatus.Ok) {
+                r.value = value(rb.readUInt32LE(o + 12));
+                r.rowHandle = rb.readUInt32LE(o + 16);
+                r.colHandle = rb.readUInt32LE(o + 20);
+            } else if (q.kind === MatrixQuery.Rect && (r.status === MatrixStatus.Ok || r.status === MatrixStatus.OutOfRange)) {
+                const at = Number(rb.readBigUInt64LE(o + 24));
+                const nr = q.nRows || 0, nc = q.nCols || 0;
+                r.values = [];
+                for (let a = 0; a < nr; a++) {
+                    const row = [];
+                    for (let b = 0; b < nc; b++) row.push(value(vb.readUInt32LE((at + a * nc + b) * 4)));
+                    r.values.push(row);
+                }
+            }
+            return r;
+        });
+    }
+    /** mte_value_text: the canonical JSON text of a value id of the loaded batch */
+    valueText(id) { this._idle(); return addon.valueText(this._engine, id); }
     /** SnapshotLegacy ITree (snapshotlegacy.ts:103-182): header, body, catch-up messages */
     snapshotLegacy(doc, catchUpBlobName = "catchupOps") {
         this._idle();
@@ -302,6 +351,7 @@ class MergeTreeClient {
 
 module.exports = {
     BatchedMergeEngine, MergeTreeClient, DocStatus, ViewKind, ViewStatus, VIEW_NO_CLIENT, VIEW_F_REMOVED,
+    MatrixQuery, MatrixStatus,
     abiVersion: addon.abiVersion, buildInfo: addon.buildInfo,
     createBuilder: addon.createBuilder, builderAddDoc: addon.builderAddDoc, builderDocCount: addon.builderDocCount,
     builderOpenDoc: addon.builderOpenDoc, builderAppendMessages: addon.builderAppendMessages,

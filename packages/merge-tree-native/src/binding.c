@@ -723,6 +723,67 @@ static napi_value js_view_props(napi_env env, napi_callback_info info) {
     return s;
 }
 
+/* matrixCells(engine, queries: Buffer of mte_cell_q records): [results: Buffer of mte_cell_r records, vals:
+ * Buffer of uint32 value ids] -- mte_matrix_cells, the sizing call and then the real one */
+static napi_value js_matrix_cells(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    mte_engine* e = (mte_engine*)get_external(env, argv[0]);
+    void* qbuf = NULL;
+    size_t qlen = 0;
+    if (napi_get_buffer_info(env, argv[1], &qbuf, &qlen) != napi_ok || qlen % sizeof(mte_cell_q))
+        return throw_mte(env, "matrixCells", MTE_E_ARG, "queries: a Buffer of 32-byte records");
+    const size_t n = qlen / sizeof(mte_cell_q);
+    mte_cell_q* q = (mte_cell_q*)malloc(qlen + 1);  /* (a Buffer's bytes need not be aligned) */
+    mte_cell_r* out = (mte_cell_r*)calloc(n + 1, sizeof(mte_cell_r));
+    if (!q || !out) {
+        free(q);
+        free(out);
+        return throw_mte(env, "matrixCells", MTE_E_NOMEM, NULL);
+    }
+    memcpy(q, qbuf, qlen);
+    size_t ids = 0;
+    uint32_t* vals = NULL;
+    int rc = mte_matrix_cells(e, q, n, out, NULL, 0, &ids);
+    if (!rc && ids) {
+        vals = (uint32_t*)malloc(ids * sizeof(uint32_t));
+        rc = vals ? mte_matrix_cells(e, q, n, out, vals, ids, &ids) : MTE_E_NOMEM;
+    }
+    napi_value arr = NULL, rb, vb;
+    if (!rc) {
+        if (napi_create_array_with_length(env, 2, &arr) != napi_ok ||
+            napi_create_buffer_copy(env, n * sizeof(mte_cell_r), out, NULL, &rb) != napi_ok ||
+            napi_create_buffer_copy(env, ids * sizeof(uint32_t), vals ? (void*)vals : (void*)out, NULL, &vb) != napi_ok)
+            rc = MTE_E_NOMEM;
+    }
+    free(q);
+    free(out);
+    free(vals);
+    if (rc) return throw_mte(env, "mte_matrix_cells", rc, e ? mte_last_error(e) : NULL);
+    napi_set_element(env, arr, 0, rb);
+    napi_set_element(env, arr, 1, vb);
+    return arr;
+}
+
+/* valueText(engine, valueId): string -- the canonical JSON text of a value id of the loaded batch */
+static napi_value js_value_text(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return NULL;
+    mte_engine* e = (mte_engine*)get_external(env, argv[0]);
+    uint32_t id;
+    napi_get_value_uint32(env, argv[1], &id);
+    size_t n = 0;
+    int rc = mte_value_text(e, id, NULL, 0, &n);
+    if (rc) return throw_mte(env, "mte_value_text", rc, e ? mte_last_error(e) : NULL);
+    char* buf = (char*)malloc(n + 1);
+    rc = buf ? mte_value_text(e, id, buf, n, &n) : MTE_E_NOMEM;
+    napi_value s = NULL;
+    if (!rc) napi_create_string_utf8(env, buf, n, &s);
+    free(buf);
+    if (rc) return throw_mte(env, "mte_value_text", rc, mte_last_error(e));
+    return s;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
     napi_property_descriptor props[] = {
         {"abiVersion", 0, js_abi_version, 0, 0, 0, napi_default, 0},
@@ -757,6 +818,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"views", 0, js_views, 0, 0, 0, napi_default, 0},
         {"clientSlot", 0, js_client_slot, 0, 0, 0, napi_default, 0},
         {"viewProps", 0, js_view_props, 0, 0, 0, napi_default, 0},
+        {"matrixCells", 0, js_matrix_cells, 0, 0, 0, napi_default, 0},
+        {"valueText", 0, js_value_text, 0, 0, 0, napi_default, 0},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;
