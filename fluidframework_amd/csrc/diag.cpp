@@ -123,6 +123,8 @@ int mte_get_info(mte_engine* e, const char* key, int64_t* value) {
     else if (k == "ck_blk_saved") *value = e->last_ck_blk_saved;      // block checkpoints written
     else if (k == "ck_blk_skipped") *value = e->last_ck_blk_skipped;  // block documents over ck_blk_budget_mb
     else if (k == "downloaded") *value = e->downloaded;  // the whole-pool download of the current results was made
+    else if (k == "map_words") *value = e->map_words;  // property-map record width of the loaded batch
+    else if (k == "mk_bitmaps_built") *value = (int64_t)e->mk.bitmaps_built;  // label bitmaps built so far (marker.cpp)
     else if (k == "mx_tables_built") *value = (int64_t)e->mx_tables_built;  // SharedMatrix cell tables built so far (matrix.cpp)
     else if (k == "out_text") {  // UTF-16 units Engine::finish gathered (counters[6..7])
         uint32_t ctr[8];

@@ -20,6 +20,7 @@
 #include "ck_plan.hpp"
 #include "engine_types.hpp"
 #include "host_batch.hpp"
+#include "marker.h"
 #include "matrix.h"
 #include "view.h"
 
@@ -268,6 +269,27 @@ struct mte_engine {
     DevBuf<MxTable> d_mx_tables;
     DevBuf<uint32_t> d_mx_pos, d_mx_ph, d_mx_totals, d_mx_handle, d_mx_vals, d_mx_flag;
 
+    // ---- marker queries (marker.cpp): what is derived from the loaded batch at the first query that needs it
+    // and kept until the batch goes (mk_drop_cache: mte_load, mte_generate) -- the three key ids, each
+    // queried label's bitmap over the value ids, the property sets that name the tile-label key and each
+    // document's "an annotate sets it" flag -- and the plan's and the results' device buffers, grown as calls
+    // need them and kept
+    struct MkCache {
+        bool keys_known = false;
+        uint32_t key_tile = 0, key_bold = 0, key_under = 0;
+        std::unordered_map<std::string, std::vector<uint32_t>> label_bits;
+        std::vector<uint8_t> set_has_tile;  // per property set (filled with keys_known)
+        std::vector<uint8_t> doc_annot;     // per document: 0 not derived yet, 1 no, 2 an annotate names the key
+        uint64_t bitmaps_built = 0;         // running count (info key "mk_bitmaps_built")
+    } mk;
+    DevBuf<MarkGroup> d_mk_groups;
+    DevBuf<MarkTileRec> d_mk_rec;
+    DevBuf<MarkJob> d_mk_jobs;
+    DevBuf<MarkCount> d_mk_count;
+    DevBuf<mte_mark_piece> d_mk_pieces;
+    DevBuf<uint32_t> d_mk_pos, d_mk_bits;
+    DevBuf<uint16_t> d_mk_text;
+
     // ---- last load and last run
     bool replayed = false;
     std::vector<DocRes> res;
@@ -361,6 +383,10 @@ int fetch_catch_up_records(mte_engine* e, uint32_t d, std::vector<uint4>& rec);
 // Every SharedMatrix cell table goes: the results they were built from are about to change. (The caller
 // has made the engine's device current.)
 void mx_drop_tables(mte_engine* e);
+
+// ---- marker.cpp
+// What the marker queries derived from the loaded batch goes: the batch is about to change.
+void mk_drop_cache(mte_engine* e);
 
 // ---- engine_ckpt.cpp: the device half of incremental replay (option retain; ck_plan.hpp is the other)
 int ck_match_batch(mte_engine* e, const mte_batch* b);  // mte_load: which documents continue

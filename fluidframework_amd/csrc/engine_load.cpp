@@ -519,6 +519,7 @@ int mte_load(mte_engine* e, const mte_batch* b) {
     if (!e || !b) return MTE_E_ARG;
     HIP_TRY(e, hipSetDevice(e->device));
     mx_drop_tables(e);
+    mk_drop_cache(e);
     copy_batch(e->hb, b, false);
     e->emit_tables = false;
     e->generated = false;
@@ -689,6 +690,7 @@ int mte_generate_ids(mte_engine* e, uint32_t kind, uint32_t n_docs, uint32_t n_o
     if (kind != 2 && kind != 3 && kind != 5) return set_err(e, MTE_E_ARG, "generator kind must be 2, 3 or 5");
     HIP_TRY(e, hipSetDevice(e->device));
     mx_drop_tables(e);
+    mk_drop_cache(e);
     e->ck.reset();  // (a new batch: no checkpoint of the last one may be continued)
     e->P.cell_mode = 0;
     e->hb = HostBatch();

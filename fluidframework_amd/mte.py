@@ -119,6 +119,17 @@ MTE_MQ_SHAPE, MTE_MQ_CELL, MTE_MQ_RECT = 0, 1, 2
 MTE_MX_OK, MTE_MX_OUT_OF_RANGE, MTE_MX_DOC_FAILED, MTE_MX_BAD_QUERY = 0, 1, 2, 3
 MTE_CELL_NONE = 0xFFFFFFFF
 
+# Marker queries (mte_markers): the query, result and piece records, and their constants.
+MARK_Q_DTYPE = np.dtype([("doc", "<u4"), ("kind", "<u4"), ("pos1", "<u4"), ("pos2", "<u4"), ("label", "<u4")])
+MARK_R_DTYPE = np.dtype([("status", "<i4"), ("row", "<u4"), ("pos", "<u4"), ("flags", "<u4"), ("count", "<u4"),
+                         ("pad", "<u4"), ("first_piece", "<u8")])
+MARK_PIECE_DTYPE = np.dtype([("row", "<u4"), ("pos", "<u4"), ("text_off", "<u8"), ("text_len", "<u4"), ("pad", "<u4")])
+assert MARK_Q_DTYPE.itemsize == 20 and MARK_R_DTYPE.itemsize == 32 and MARK_PIECE_DTYPE.itemsize == 24
+MTE_MQ_TILE_BEFORE, MTE_MQ_TILE_AFTER, MTE_MQ_PARAGRAPHS = 0, 1, 2
+MTE_MARK_OK, MTE_MARK_NOT_FOUND, MTE_MARK_UNSUPPORTED, MTE_MARK_DOC_FAILED, MTE_MARK_BAD_QUERY = 0, 1, 2, 3, 4
+MTE_MARK_F_REMOVED = 1
+MTE_MARK_TO_END = 0xFFFFFFFF
+
 # Every symbol declared in include/mte.h (checked by tests/test_abi.py).
 EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mte_last_error", "mte_load",
            "mte_replay", "mte_generate", "mte_generate_ids", "mte_export_batch", "mte_doc_status", "mte_text", "mte_length", "mte_segments",
@@ -127,7 +138,7 @@ EXPORTS = ["mte_abi_version", "mte_build_info", "mte_create", "mte_destroy", "mt
            "mte_builder_add_matrix_log", "mte_builder_add_matrix_from_summary", "mte_snapshot_matrix",
            "mte_builder_batch", "mte_builder_open_doc", "mte_builder_append_messages", "mte_retain",
            "mte_builder_open_doc_from_summary", "mte_views", "mte_client_slot", "mte_view_props",
-           "mte_matrix_cells", "mte_value_text",
+           "mte_matrix_cells", "mte_value_text", "mte_markers",
            "mte_builder_error", "mte_builder_destroy"]
 
 _lib = None
@@ -202,6 +213,9 @@ def lib():
         if hasattr(L, "mte_matrix_cells"):  # (A/B runs load older experiment builds)
             L.mte_matrix_cells.argtypes = [vp, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
             L.mte_value_text.argtypes = [vp, u32, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
+        if hasattr(L, "mte_markers"):
+            L.mte_markers.argtypes = [vp, ctypes.c_void_p, sz, ctypes.POINTER(ctypes.c_char_p), sz, ctypes.c_void_p,
+                                      ctypes.c_void_p, sz, ctypes.POINTER(sz), ctypes.c_void_p, sz, ctypes.POINTER(sz)]
         L.mte_builder_error.argtypes = [vp]
         L.mte_builder_error.restype = ctypes.c_char_p
         L.mte_builder_destroy.argtypes = [vp]
@@ -456,6 +470,53 @@ class Engine:
             self._check(fn(self._h, q.ctypes.data, len(q), out.ctypes.data, vals.ctypes.data, n.value, ctypes.byref(n)),
                         "mte_matrix_cells")
         return out, vals
+
+    def markers(self, queries, labels):
+        """mte_markers: findTile and getTextAndMarkers in the observer's current view, on the GPU, without
+        the whole-batch download. queries: a MARK_Q_DTYPE array, or an iterable of (doc, kind, pos1, pos2,
+        label index); labels: the call's label strings. Returns (results: MARK_R_DTYPE array in query
+        order, pieces: MARK_PIECE_DTYPE array, text: uint16 array); PARAGRAPHS result i owns
+        pieces[first_piece : first_piece + count], piece k's text is text[text_off : text_off + text_len]."""
+        if not (isinstance(queries, np.ndarray) and queries.dtype == MARK_Q_DTYPE):
+            queries = np.array([tuple(int(x) for x in t) for t in queries], dtype=MARK_Q_DTYPE)
+        q = np.ascontiguousarray(queries)
+        names = (ctypes.c_char_p * max(len(labels), 1))(*[s.encode("utf-8", "surrogatepass") for s in labels])
+        out = np.zeros(len(q), dtype=MARK_R_DTYPE)
+        np_, nt = ctypes.c_size_t(), ctypes.c_size_t()
+        fn = lib().mte_markers
+        self._check(fn(self._h, q.ctypes.data, len(q), names, len(labels), out.ctypes.data, None, 0, ctypes.byref(np_),
+                       None, 0, ctypes.byref(nt)), "mte_markers")
+        pieces = np.zeros(np_.value, dtype=MARK_PIECE_DTYPE)
+        text = np.zeros(nt.value, dtype=np.uint16)
+        if np_.value:
+            self._check(fn(self._h, q.ctypes.data, len(q), names, len(labels), out.ctypes.data, pieces.ctypes.data,
+                           np_.value, ctypes.byref(np_), text.ctypes.data, nt.value, ctypes.byref(nt)), "mte_markers")
+        return out, pieces, text
+
+    def find_tile(self, doc, pos, label, preceding=True):
+        """Client.findTile(pos, label, preceding) of document doc: dict(pos, row, removed), or None for the
+        reference's undefined. Raises MteError when the document is refused (MTE_MARK_UNSUPPORTED) or failed."""
+        r, _, _ = self.markers([(doc, MTE_MQ_TILE_BEFORE if preceding else MTE_MQ_TILE_AFTER, pos, 0, 0)], [label])
+        s = int(r[0]["status"])
+        if s == MTE_MARK_NOT_FOUND:
+            return None
+        if s != MTE_MARK_OK:
+            raise MteError(f"findTile: marker status {s}")
+        return {"pos": int(r[0]["pos"]), "row": int(r[0]["row"]), "removed": bool(r[0]["flags"] & MTE_MARK_F_REMOVED)}
+
+    def get_text_and_markers(self, doc, label, start=None, end=None):
+        """SharedString.getTextAndMarkers(label) of document doc (with start / end: the helper's range):
+        (parallelText: list of str, parallelMarkers: list of dict(pos, row))."""
+        r, pieces, text = self.markers([(doc, MTE_MQ_PARAGRAPHS, start or 0, MTE_MARK_TO_END if end is None else end, 0)],
+                                       [label])
+        if r[0]["status"] != MTE_MARK_OK:
+            raise MteError(f"getTextAndMarkers: marker status {int(r[0]['status'])}")
+        texts, marks = [], []
+        for p in pieces:
+            a = int(p["text_off"])
+            texts.append(text[a: a + int(p["text_len"])].tobytes().decode("utf-16-le", "surrogatepass"))
+            marks.append({"pos": int(p["pos"]), "row": int(p["row"])})
+        return texts, marks
 
     def value_text(self, value_id):
         """The canonical JSON text of a value id of the loaded batch (0: "null")."""
@@ -717,6 +778,21 @@ class MergeTreeClient:
         """The properties of the segment at pos, or None (client.ts:1012-1020)."""
         r = self._locate(pos)
         return self._engine.view_props(0, int(r["row"])) if r["status"] == MTE_VIEW_OK else None
+
+    def findTile(self, pos, label, preceding=True):  # noqa: N802
+        """Client.findTile (client.ts:1081-1084) in the current view, read on the GPU: {"pos", "row"} -- row
+        indexes the segment table -- or None for the reference's undefined."""
+        t = self._run().find_tile(0, pos, label, preceding)
+        return None if t is None else {"pos": t["pos"], "row": t["row"]}
+
+    def getTextAndMarkers(self, label):  # noqa: N802
+        """SharedString.getTextAndMarkers (sharedString.ts:207-210), read on the GPU: {"parallelText",
+        "parallelMarkers"}, each marker {"pos", "row", "properties"}."""
+        e = self._run()
+        texts, marks = e.get_text_and_markers(0, label)
+        for m in marks:
+            m["properties"] = e.view_props(0, m["row"])
+        return {"parallelText": texts, "parallelMarkers": marks}
 
     def getPosition(self, row):  # noqa: N802
         """The current position of segment table row `row` (client.ts:295-300): the start of the first

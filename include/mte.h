@@ -438,6 +438,68 @@ int mte_matrix_cells(mte_engine* e, const mte_cell_q* q, size_t n, mte_cell_r* o
  * id 0 is null). buf may be NULL to query *len. MTE_E_RANGE for an id the batch does not have. */
 int mte_value_text(mte_engine* e, uint32_t value_id, char* buf, size_t cap, size_t* len);
 
+/* ---- marker queries ----------------------------------------------------------------------------
+ * The structure reads of a SharedString -- Client.findTile (client.ts:1081-1084, mergeTree.ts:1763-1789)
+ * and SharedString.getTextAndMarkers (sharedString.ts:207-210, textSegment.ts:127-152, 188-275) --
+ * answered on the GPU from the pass's output rows and their property maps, many documents a call,
+ * without the whole-batch download. All of it is the observer's current view: a row counts its local net
+ * length (0 when removed at all, a marker 1). A row is a tile for label L (refHasTileLabel,
+ * mergeTree.ts:581-597) when it is a marker whose refType has ReferenceType.Tile (0x1), whose properties
+ * hold "referenceTileLabels", and `for (x of value)` yields x === L: a string element of an array, or a
+ * code point of a string. Any other truthy value (the reference throws there) matches nothing. */
+enum {
+    MTE_MQ_TILE_BEFORE = 0, /* findTile(pos1, L, true) (search + tileShift / recordTileStart, mergeTree.ts:996-1035,
+                               1791-1829): the last visible tile row whose position is <= pos1; at or past the
+                               length, the last visible tile of the document */
+    MTE_MQ_TILE_AFTER = 1,  /* findTile(pos1, L, false) (backwardSearch, mergeTree.ts:1831-1874): pos1 > length is
+                               NOT_FOUND; else the first visible tile row whose position is >= pos1. At pos1 ==
+                               length the document's last row is the containing leaf whatever its length, and
+                               recordTileStart does not test visibility: a tile there is the answer even when
+                               removed (MTE_MARK_F_REMOVED, pos = the length), anything else is NOT_FOUND */
+    MTE_MQ_PARAGRAPHS = 2,  /* getTextAndMarkers(L, pos1, pos2) (pos2 = 0xFFFFFFFF: to the end): one piece per
+                               visible tile of [pos1, pos2), carrying the text gathered since the piece before
+                               (textSegment.ts gatherText, parallelArrays: the <b> / <u> tags of "font-weight" /
+                               "text-decoration" included). Text after the last tile is dropped, as there */
+};
+enum {                          /* mte_mark_r.status; none of them fails the call */
+    MTE_MARK_OK = 0,
+    MTE_MARK_NOT_FOUND = 1,     /* TILE: the reference's undefined */
+    MTE_MARK_UNSUPPORTED = 2,   /* TILE: an annotate of the document's log sets "referenceTileLabels": the
+                                   reference answers from block caches annotateRange does not refresh, so its
+                                   answer depends on tree shape. PARAGRAPHS is never refused */
+    MTE_MARK_DOC_FAILED = 3,    /* the document's replay status is not MTE_DOC_OK */
+    MTE_MARK_BAD_QUERY = 4,     /* doc or label out of range, unknown kind, pos2 < pos1 */
+};
+#define MTE_MARK_F_REMOVED 0x1u /* TILE_AFTER at pos1 == length: the row is a removed tile */
+typedef struct mte_mark_q {
+    uint32_t doc;
+    uint32_t kind;        /* MTE_MQ_TILE_BEFORE / _TILE_AFTER / _PARAGRAPHS */
+    uint32_t pos1, pos2;  /* pos2: PARAGRAPHS only */
+    uint32_t label;       /* index into the call's labels */
+} mte_mark_q;
+typedef struct mte_mark_r {   /* 32 bytes */
+    int32_t status;           /* MTE_MARK_* */
+    uint32_t row;             /* TILE: the tile's index in mte_segments order (mte_view_props reads its properties) */
+    uint32_t pos;             /* TILE: getPosition(marker): the visible units before it */
+    uint32_t flags;           /* MTE_MARK_F_* */
+    uint32_t count;           /* PARAGRAPHS: its pieces */
+    uint32_t pad;
+    uint64_t first_piece;     /* PARAGRAPHS: index of its first piece in the call's pieces */
+} mte_mark_r;
+typedef struct mte_mark_piece {   /* 24 bytes: parallelMarkers[i] / parallelText[i] */
+    uint32_t row, pos;            /* the tile that closes the piece, as in a TILE result */
+    uint64_t text_off;            /* its text: text[text_off .. text_off + text_len) */
+    uint32_t text_len;
+    uint32_t pad;
+} mte_mark_piece;
+/* out[i] answers q[i]; labels are n_labels NUL-terminated UTF-8 strings. The PARAGRAPHS queries' pieces go
+ * to pieces (pieces_cap records; *n_pieces = the records they need) and their UTF-16 units to text (text_cap
+ * units; *text_len likewise), both in query order. pieces or text may be NULL to size the buffers (out is
+ * still filled); a capacity too small is MTE_E_RANGE with both sizes set. MTE_E_STATE before a replay. */
+int mte_markers(mte_engine* e, const mte_mark_q* q, size_t n, const char* const* labels, size_t n_labels, mte_mark_r* out,
+                mte_mark_piece* pieces, size_t pieces_cap, size_t* n_pieces, uint16_t* text, size_t text_cap,
+                size_t* text_len);
+
 /* Multi-GPU: documents are sharded by id across ranks (one process per GPU) and the
  * only collective of the path is this all-gather of the per-document summary records, over RCCL
  * (xGMI inside a node). The communicator is RCCL's own: rank 0 makes an id (mte_rccl_unique_id),

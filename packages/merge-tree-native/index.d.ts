@@ -45,6 +45,29 @@ export interface DocLog { observer?: string; messages?: ISequencedDocumentMessag
      *  `summary` (a SharedMatrix summary ITree, SharedMatrix.loadCore) they are the suffix after it */
     matrix?: ISequencedDocumentMessage[]; }
 
+/** Marker queries (BatchedMergeEngine.markers): what to read, and how each query ended. */
+export declare const MarkerQuery: { readonly TileBefore: 0; readonly TileAfter: 1; readonly Paragraphs: 2 };
+export declare const MarkerStatus: { readonly Ok: 0; readonly NotFound: 1; readonly Unsupported: 2; readonly DocFailed: 3;
+    readonly BadQuery: 4 };
+export interface MarkerQueryRecord {
+    doc: number;
+    kind: number;
+    pos1?: number;
+    /** Paragraphs: the range's end; undefined = to the end */
+    pos2?: number;
+    label: string;
+}
+export interface MarkerPiece { row: number; pos: number; text: string }
+export interface MarkerResult {
+    status: number;
+    /** TileBefore / TileAfter: the tile's row of the segment table, its position, and whether it is removed */
+    row?: number;
+    pos?: number;
+    removed?: boolean;
+    /** Paragraphs: one piece per tile of the range */
+    pieces?: MarkerPiece[];
+}
+
 export declare class BatchedMergeEngine {
     constructor(options?: { device?: number; chunkSize?: number; newMergeTreeSnapshotFormat?: boolean });
     load(docs: DocLog[]): void;
@@ -85,6 +108,9 @@ export declare class BatchedMergeEngine {
     /** mte_matrix_cells: rowCount / colCount, getCell and dense ranges of the replayed matrices, many matrices a
      *  call, answered on the GPU without the summary blob. results[i] answers queries[i]. */
     matrixCells(queries: MatrixCellQuery[]): MatrixCellResult[];
+    /** mte_markers: findTile and getTextAndMarkers in the observer's current view, answered on the GPU from the
+     *  last replay's rows and their property maps. */
+    markers(queries: MarkerQueryRecord[]): MarkerResult[];
     /** mte_value_text: the canonical JSON text of a value id of the loaded batch. */
     valueText(id: number): string;
 }
@@ -110,6 +136,11 @@ export declare class MergeTreeClient {
     getLength(): number;
     /** Client.getContainingSegment: segment = the row of the segment table; both undefined past the end. */
     getContainingSegment(pos: number): { segment: number | undefined; offset: number | undefined };
+    /** Client.findTile: { pos, row } -- row indexes the segment table -- or undefined */
+    findTile(pos: number, label: string, preceding?: boolean): { pos: number; row: number } | undefined;
+    /** SharedString.getTextAndMarkers */
+    getTextAndMarkers(label: string): { parallelText: string[];
+        parallelMarkers: { pos: number; row: number; properties: Record<string, unknown> | null }[] };
     /** Client.getPropertiesAtPosition */
     getPropertiesAtPosition(pos: number): Record<string, unknown> | undefined;
     /** Client.getPosition of segment table row `row` */

@@ -21,6 +21,10 @@ const MatrixQuery = Object.freeze({ Shape: 0, Cell: 1, Rect: 2 });
 const MatrixStatus = Object.freeze({ Ok: 0, OutOfRange: 1, DocFailed: 2, BadQuery: 3 });
 const CELL_NONE = 0xFFFFFFFF;
 
+/** Marker queries (mte_markers): kinds and per-query statuses. */
+const MarkerQuery = Object.freeze({ TileBefore: 0, TileAfter: 1, Paragraphs: 2 });
+const MarkerStatus = Object.freeze({ Ok: 0, NotFound: 1, Unsupported: 2, DocFailed: 3, BadQuery: 4 });
+
 class BatchedMergeEngine {
     constructor(options = {}) {
         this.device = options.device || 0;
@@ -119,6 +123,44 @@ class BatchedMergeEngine {
             if (q.kind === ViewKind.Text && r.status === ViewStatus.Ok) {
                 const at = Number(rb.readBigUInt64LE(o + 24));
                 r.text = tb.toString("utf16le", at * 2, (at + r.length) * 2);
+            }
+            return r;
+        });
+    }
+    /**
+     * mte_markers: findTile and getTextAndMarkers in the observer's current view, answered on the GPU from the
+     * last replay's rows and their property maps. queries: [{ doc, kind, pos1, pos2, label }] -- label a string.
+     * Returns, in query order, [{ status, row?, pos?, removed?, pieces? }]: TileBefore / TileAfter -> row / pos
+     * (Client.findTile; status NotFound for its undefined, Unsupported when an annotate of the document's log sets
+     * referenceTileLabels); Paragraphs -> pieces, [{ row, pos, text }], one per tile of [pos1, pos2).
+     */
+    markers(queries) {
+        this._idle();
+        const labels = [], slot = new Map();
+        const qb = Buffer.alloc(queries.length * 20);
+        queries.forEach((q, i) => {
+            if (!slot.has(q.label)) { slot.set(q.label, labels.length); labels.push(String(q.label)); }
+            [q.doc, q.kind, q.pos1 || 0, q.pos2 === undefined ? 0xFFFFFFFF : q.pos2, slot.get(q.label)].forEach((v, k) => {
+                qb.writeUInt32LE(v >>> 0, i * 20 + 4 * k);
+            });
+        });
+        const [rb, pb, tb] = addon.markers(this._engine, qb, labels);
+        return queries.map((q, i) => {
+            const o = i * 32;
+            const r = { status: rb.readInt32LE(o) };
+            if (r.status !== MarkerStatus.Ok) return r;
+            if (q.kind !== MarkerQuery.Paragraphs) {
+                r.row = rb.readUInt32LE(o + 4);
+                r.pos = rb.readUInt32LE(o + 8);
+                r.removed = (rb.readUInt32LE(o + 12) & 1) !== 0;
+                return r;
+            }
+            const n = rb.readUInt32LE(o + 16), first = Number(rb.readBigUInt64LE(o + 24));
+            r.pieces = [];
+            for (let k = first; k < first + n; k++) {
+                const at = Number(pb.readBigUInt64LE(k * 24 + 8)), len = pb.readUInt32LE(k * 24 + 16);
+                r.pieces.push({ row: pb.readUInt32LE(k * 24), pos: pb.readUInt32LE(k * 24 + 4),
+                    text: tb.toString("utf16le", at * 2, (at + len) * 2) });
             }
             return r;
         });
@@ -320,6 +362,23 @@ class MergeTreeClient {
         const p = this._engine.viewProps(0, r.row);
         return p === null ? undefined : p;
     }
+    /** Client.findTile (client.ts:1081-1084) in the current view, read on the GPU: { pos, row } -- row indexes
+     *  the segment table -- or undefined. */
+    findTile(pos, label, preceding = true) {
+        const r = this._run().markers([{ doc: 0, kind: preceding ? MarkerQuery.TileBefore : MarkerQuery.TileAfter, pos1: pos, label }])[0];
+        if (r.status === MarkerStatus.NotFound) return undefined;
+        if (r.status !== MarkerStatus.Ok) throw new Error(`findTile: marker status ${r.status}`);
+        return { pos: r.pos, row: r.row };
+    }
+    /** SharedString.getTextAndMarkers (sharedString.ts:207-210), read on the GPU: { parallelText,
+     *  parallelMarkers }, each marker { pos, row, properties }. */
+    getTextAndMarkers(label) {
+        const e = this._run();
+        const r = e.markers([{ doc: 0, kind: MarkerQuery.Paragraphs, label }])[0];
+        if (r.status !== MarkerStatus.Ok) throw new Error(`getTextAndMarkers: marker status ${r.status}`);
+        return { parallelText: r.pieces.map((p) => p.text),
+            parallelMarkers: r.pieces.map((p) => ({ pos: p.pos, row: p.row, properties: e.viewProps(0, p.row) })) };
+    }
     /** Client.getPosition (client.ts:295-300) of segment table row `row`: the start of the first visible
      *  row at or after it (found by locating positions: O(log length) queries). */
     getPosition(row) {
@@ -351,7 +410,7 @@ class MergeTreeClient {
 
 module.exports = {
     BatchedMergeEngine, MergeTreeClient, DocStatus, ViewKind, ViewStatus, VIEW_NO_CLIENT, VIEW_F_REMOVED,
-    MatrixQuery, MatrixStatus,
+    MatrixQuery, MatrixStatus, MarkerQuery, MarkerStatus,
     abiVersion: addon.abiVersion, buildInfo: addon.buildInfo,
     createBuilder: addon.createBuilder, builderAddDoc: addon.builderAddDoc, builderDocCount: addon.builderDocCount,
     builderOpenDoc: addon.builderOpenDoc, builderAppendMessages: addon.builderAppendMessages,

@@ -688,6 +688,63 @@ static napi_value js_views(napi_env env, napi_callback_info info) {
     return arr;
 }
 
+/* markers(engine, queries: Buffer of mte_mark_q records, labels: string[]): [results: Buffer of mte_mark_r
+ * records, pieces: Buffer of mte_mark_piece records, text: Buffer of UTF-16 units] -- mte_markers, the sizing
+ * call and then the real one */
+static napi_value js_markers(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return NULL;
+    mte_engine* e = (mte_engine*)get_external(env, argv[0]);
+    void* qbuf = NULL;
+    size_t qlen = 0;
+    uint32_t n_labels = 0;
+    if (napi_get_buffer_info(env, argv[1], &qbuf, &qlen) != napi_ok || qlen % sizeof(mte_mark_q))
+        return throw_mte(env, "markers", MTE_E_ARG, "queries: a Buffer of 20-byte records");
+    if (napi_get_array_length(env, argv[2], &n_labels) != napi_ok) return throw_mte(env, "markers", MTE_E_ARG, "labels: an array of strings");
+    const size_t n = qlen / sizeof(mte_mark_q);
+    mte_mark_q* q = (mte_mark_q*)malloc(qlen + 1);  /* (a Buffer's bytes need not be aligned) */
+    mte_mark_r* out = (mte_mark_r*)calloc(n + 1, sizeof(mte_mark_r));
+    char** labels = (char**)calloc((size_t)n_labels + 1, sizeof(char*));
+    mte_mark_piece* pieces = NULL;
+    uint16_t* text = NULL;
+    size_t n_pieces = 0, units = 0;
+    int rc = (q && out && labels) ? MTE_OK : MTE_E_NOMEM;
+    for (uint32_t l = 0; !rc && l < n_labels; l++) {
+        napi_value s;
+        if (napi_get_element(env, argv[2], l, &s) != napi_ok || !(labels[l] = get_string(env, s, NULL))) rc = MTE_E_ARG;
+    }
+    if (!rc) {
+        memcpy(q, qbuf, qlen);
+        rc = mte_markers(e, q, n, (const char* const*)labels, n_labels, out, NULL, 0, &n_pieces, NULL, 0, &units);
+    }
+    if (!rc && n_pieces) {
+        pieces = (mte_mark_piece*)malloc(n_pieces * sizeof(mte_mark_piece));
+        text = (uint16_t*)malloc(units * 2 + 2);
+        rc = (pieces && text) ? mte_markers(e, q, n, (const char* const*)labels, n_labels, out, pieces, n_pieces, &n_pieces, text,
+                                            units, &units)
+                              : MTE_E_NOMEM;
+    }
+    napi_value arr = NULL, rb, pb, tb;
+    if (!rc) {
+        if (napi_create_array_with_length(env, 3, &arr) != napi_ok ||
+            napi_create_buffer_copy(env, n * sizeof(mte_mark_r), out, NULL, &rb) != napi_ok ||
+            napi_create_buffer_copy(env, n_pieces * sizeof(mte_mark_piece), pieces ? (void*)pieces : (void*)out, NULL, &pb) != napi_ok ||
+            napi_create_buffer_copy(env, units * 2, text ? (void*)text : (void*)out, NULL, &tb) != napi_ok)
+            rc = MTE_E_NOMEM;
+    }
+    for (uint32_t l = 0; labels && l < n_labels; l++) free(labels[l]);
+    free(labels);
+    free(q);
+    free(out);
+    free(pieces);
+    free(text);
+    if (rc) return throw_mte(env, "mte_markers", rc, rc == MTE_E_ARG ? "labels: an array of strings" : e ? mte_last_error(e) : NULL);
+    napi_set_element(env, arr, 0, rb);
+    napi_set_element(env, arr, 1, pb);
+    napi_set_element(env, arr, 2, tb);
+    return arr;
+}
+
 /* clientSlot(engine, doc, clientId): number -- the short id, 0xFFFFFFFF when the document has none for it */
 static napi_value js_client_slot(napi_env env, napi_callback_info info) {
     napi_value argv[3];
@@ -816,6 +873,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"rcclCommDestroy", 0, js_rccl_comm_destroy, 0, 0, 0, napi_default, 0},
         {"gatherSummaries", 0, js_gather_summaries, 0, 0, 0, napi_default, 0},
         {"views", 0, js_views, 0, 0, 0, napi_default, 0},
+        {"markers", 0, js_markers, 0, 0, 0, napi_default, 0},
         {"clientSlot", 0, js_client_slot, 0, 0, 0, napi_default, 0},
         {"viewProps", 0, js_view_props, 0, 0, 0, napi_default, 0},
         {"matrixCells", 0, js_matrix_cells, 0, 0, 0, napi_default, 0},
